@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the WBC per-tick hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config {2,3,4}] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config {2,3,4,5}] [--dump-outputs DIR] [--full [--no-cpu] ...]
+
+A plain run sets up, warms up, times exactly K steps once and prints the contract fields (metric, value, unit, ms_per_step, ...);
+--full adds everything else the line has carried: per-kernel timing, roofline objects, CPU-oracle baselines and the extra legs.
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (inputs are seeded: identical run to run).
 
 One "step" = one control tick (dynamics sweep -> observer -> GRF QP -> torque map) over one batch of
 synthetic states already resident in HBM.  Default workload = BASELINE.json configs[1]:
@@ -194,6 +198,30 @@ def leg_fields(workload, k, units_per_step, world, el, bl, gather, dtype, unit_m
             "rccl_ranks": world, "dtype": dtype}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (torch tensors or numpy arrays, states along the last axis) as path/<name>.npy -- float32 stays
+    float32, everything else (fp64 results, int32 status / iters) is written as float64.  Above DUMP_MAX_BYTES in all, the same fixed, seeded
+    sample of states is taken from every array and its indices are written as state_index.npy."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        n = next(iter(host.values())).shape[-1]
+        keep = max(1, int(DUMP_MAX_BYTES // (total / n + 8)))
+        idx = np.sort(np.random.default_rng(20240607).choice(n, keep, replace=False))
+        host = {name: np.ascontiguousarray(a[..., idx]) for name, a in host.items()}
+        host["state_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -220,6 +248,13 @@ def main():
     ap.add_argument("--no-closed-loop", action="store_true", help="default run: do not start the closed-loop child")
     ap.add_argument("--single-process", action="store_true",
                     help="N > 1 without torchrun: ONE process drives N devices through the C-ABI's wbc_multi_* path")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel event timing and roofline objects, CPU-oracle baselines, latency / dense-QP / "
+                         "large-batch / closed-loop legs, the N > 1 gather and scale legs (the options above that switch legs act only with --full). "
+                         "Without it the run sets up, warms up, times exactly --steps ticks once and prints the contract fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64, float32 for an "
+                         "fp32 run; at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.single_process:
@@ -299,6 +334,22 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
+    workload = ("configs[%d]: batch=%d states/GPU, %s, observer %s, %s; synthetic quadruped URDF (DogBot URDF absent)"
+                % (args.config - 1, n, "4-contact stance" if args.config == 2 else "mixed 2/3/4-foot trot masks", "on" if obs else "off", dtype))
+    returned = dict(out, **({"obs_integ": integ, "obs_r": rr} if obs else {}))   # what the caller of the tick receives (observer state: in place)
+    if not args.full:
+        # the plain run: ONE block of exactly `steps` ticks (barrier + synchronize on both sides, max over ranks), nothing else on the device
+        blocks = timed_blocks(step, args.steps, dist, torch, min_total_s=0.0, max_blocks=1, min_blocks=1)
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, returned)
+            res = contract_fields(args.steps, args.warmup, n, world, blocks[0], dtype, workload, want_mats)
+            res["timing"] = {"blocks": 1, "steps_per_block": args.steps, "note": "value and ms_per_step: one block of exactly `steps` ticks after "
+                             "`warmup` + 1 untimed ticks; --full adds the per-kernel, roofline, baseline and characterisation legs"}
+            print_line(res)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # HIP events bracket both kernels of every SAMPLE-th tick of the timed region (on the launch stream): recording
     # events around every launch costs ~15 us per tick at this batch size, which would be a quarter of the step.
     sample = max(1, args.sample_every)
@@ -310,6 +361,8 @@ def main():
         solver.enable_timing(0)
     # (tests/test_sharding_gloo.py drives measure_job / gather_leg / contract_fields / job_fields with eight gloo ranks and stand-in ticks)
     blocks, elapsed, long_blocks = measure_job(step, args.steps, n, world, dist, torch, np, after_blocks=close_sampling)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, returned)
     tm = tmbox["tm"]
     status = out["status"].cpu().numpy()
     iters = out["iters"].cpu().numpy()
@@ -376,9 +429,7 @@ def main():
         rows_in = (78 + (60 if obs else 0)) if fused else 38
         rows_out = words - rows_in
         pattern = pattern_ceiling(ts, rows_in, rows_out, n) if world == 1 else None
-        res = contract_fields(args.steps, args.warmup, n, world, elapsed, dtype,
-                              "configs[%d]: batch=%d states/GPU, %s, observer %s, %s; synthetic quadruped URDF (DogBot URDF absent)"
-                              % (args.config - 1, n, "4-contact stance" if args.config == 2 else "mixed 2/3/4-foot trot masks", "on" if obs else "off", dtype), want_mats)
+        res = contract_fields(args.steps, args.warmup, n, world, elapsed, dtype, workload, want_mats)
         res.update({
             "roofline": {"kernel": (("tile_tick_kernel (sweep + observer roles of a 64 / 96 / 128-state workgroup, then the staged QP tile of the same states: one launch)" if tile_tick
                                      else ("fused_pair_kernel (two 16-state tick workgroups as one twelve-wavefront workgroup of 32 states)" if pair_tick else "fused_tick_kernel")) if fused else tick_sweep_name(dtype, obs, n, split)),
@@ -792,6 +843,38 @@ def multi_capi_bench(args, W, synth, torch, np):
             integ.append(sv.dynamics(ins["q"][i], ins["v"][i], want=("p",))["p"].clone())
         obs_state = (integ, [torch.zeros_like(x) for x in integ])
     tick, outs = ms.prepare_step(n_total, ins, obs_state, want_mats=not args.no_mats)
+    contract = lambda el: {
+        "metric": "WBC control-steps/sec (batched DogBot)", "value": args.steps * n_total / el, "unit": "control-steps/s",
+        "n_gpus": k, "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+        "config": {"workload": "configs[%d] per shard: batch=%d states, observer %s, %s; ONE process, %d shards through wbc_multi_* "
+                               "on devices %s" % (args.config - 1, args.batch, "on" if obs else "off", dtype, k, devices),
+                   "batch_per_gpu": args.batch, "parallelism": "single process, batch-sharded x%d (C-ABI wbc_multi_step_batch), no data-path collective" % k,
+                   "distinct_devices": distinct}}
+
+    def returned():   # what the caller of the tick receives, the shards side by side (observer state: in place)
+        cat = lambda ts: torch.cat([t.cpu() for t in ts], dim=-1)
+        r = {name: cat([o[name] for o in outs]) for name in outs[0]}
+        if obs_state is not None:
+            r.update(obs_integ=cat(obs_state[0]), obs_r=cat(obs_state[1]))
+        return r
+    if not args.full:
+        # the plain run: warm-up ticks, ONE block of exactly `steps` ticks on every shard, the outputs of the last one
+        for _ in range(args.warmup):
+            tick()
+        ms.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            tick()
+        ms.synchronize()
+        el = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, returned())
+        res = contract(el)
+        res["timing"] = {"blocks": 1, "steps_per_block": args.steps, "note": "value and ms_per_step: one block of exactly `steps` ticks after `warmup` "
+                         "untimed ones; --full adds the gather and issue-thread legs"}
+        print_line(res)
+        return
     tick_b, outs_b = ms.prepare_step(n_total, ins, obs_state, want_mats=not args.no_mats)   # second tau buffer for the overlapped gather
     tau_all = ms.allgather_tau(n_total, outs)
     tau_all_b = ms.allgather_tau(n_total, outs_b)
@@ -823,6 +906,8 @@ def multi_capi_bench(args, W, synth, torch, np):
         tick()
     run(0)              # one untimed pass of blocks: the first measured mode otherwise carries clock / allocator warm-up (155 M against 294 M for the same ticks)
     blocks, host0 = run(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, returned())
     sblocks, host1 = run(1)
     gblocks, host2 = run(2)
     el, gel, sel = float(np.median(blocks)), float(np.median(gblocks)), float(np.median(sblocks))
@@ -855,14 +940,8 @@ def multi_capi_bench(args, W, synth, torch, np):
         except Exception as e:
             host_issue[tag] = {"error": repr(e)[:200]}
     ok = float(np.mean([(o["status"] == 0).double().mean().item() for o in outs]))
-    print_line({
-        "metric": "WBC control-steps/sec (batched DogBot)", "value": args.steps * n_total / el, "unit": "control-steps/s",
-        "n_gpus": k, "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-        "config": {"workload": "configs[%d] per shard: batch=%d states, observer %s, %s; ONE process, %d shards through wbc_multi_* "
-                               "on devices %s" % (args.config - 1, args.batch, "on" if obs else "off", dtype, k, devices),
-                   "batch_per_gpu": args.batch, "parallelism": "single process, batch-sharded x%d (C-ABI wbc_multi_step_batch), no data-path collective" % k,
-                   "distinct_devices": distinct},
+    res = contract(el)
+    res.update({
         "timing": {"blocks": len(blocks), "steps_per_block": args.steps, "block_ms_median": el * 1e3, "block_ms_min": min(blocks) * 1e3,
                    "block_ms_max": max(blocks) * 1e3},
         "with_tau_allgather": {"value": args.steps * n_total / gel, "ms_per_step": gel / args.steps * 1e3,
@@ -872,6 +951,7 @@ def multi_capi_bench(args, W, synth, torch, np):
                                           "collective": "wbc_multi_allgather_tau on the shard streams behind every tick"}},
         "host_issue": host_issue,
         "rccl_ranks": ms.rccl_ranks, "qp": {"status_ok_frac": ok}, "roofline": None, "cpu_baseline": None})
+    print_line(res)
 
 
 def rollout_setup(args, W, synth, torch, np, model, dtype, n, H, rank, local_rank, tracking):
@@ -970,8 +1050,40 @@ def rollout_bench(args, W, synth, torch, np, dist, world, rank, local_rank):
     for _ in range(max(1, args.warmup)):
         one_rollout()
     torch.cuda.synchronize()
+    warm_on = os.environ.get("WBC_ROLLOUT_WARM", "1") != "0"
+    contract = lambda elapsed: {
+        "metric": "WBC control-steps/sec (batched DogBot)", "value": args.steps * H * n * world / elapsed,
+        "unit": "control-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": dtype, "data": "synthetic",
+        "config": {"workload": "configs[4]: horizon=%d x batch=%d rollouts per GPU, trot masks, observer on, pushes, %s; "
+                               "one step = one rollout (%d dependent ticks incl. %sforward dynamics + integrator)"
+                               % (H, n, dtype, H, "CoM planner/reference generator + " if args.tracking else ""),
+                   "batch_per_gpu": n, "horizon": H, "parallelism": "batch-sharded x%d, rank-local for all ticks" % world,
+                   "qp_warm_start": ("ticks after the first start their QPs from the previous tick's active set (wbc_solver_options.rollout_warm = 1; "
+                                     "results do not depend on it)" if warm_on else "off (rollout_warm = 0): every tick solves from the unconstrained minimum"),
+                   "launches": ("one persistent rollout_kernel launch per rollout" if (n <= 4096 and os.environ.get("WBC_ROLLOUT_PERSISTENT", "1") != "0")
+                                else "per tick: %sdyn_sweep/fused tick, qp, integrate" % ("reference, " if args.tracking else ""))},
+        "us_per_tick": elapsed / args.steps / H * 1e6}
+    inp, integ, rr = r5["keep"][0], r5["keep"][6], r5["keep"][7]
+    returned = dict(out, q=inp["q"], v=inp["v"], obs_integ=integ, obs_r=rr)   # the rollout's outputs and the state it advanced in place
+    if not args.full:
+        # the plain run: ONE block of exactly `steps` rollouts, the outputs of the last one, the contract fields
+        blocks = timed_blocks(one_rollout, args.steps, dist, torch, min_total_s=0.0, max_blocks=1, min_blocks=1)
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, returned)
+            res = contract(blocks[0])
+            res["timing"] = {"blocks": 1, "steps_per_block": args.steps, "note": "value and ms_per_step: one block of exactly `steps` rollouts after "
+                             "`warmup` untimed ones; --full adds the roofline and CPU-baseline legs"}
+            print_line(res)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     blocks = timed_blocks(one_rollout, args.steps, dist, torch)
     elapsed = float(np.median(blocks))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, returned)
     ok = float((out["status"].cpu().numpy() == 0).mean())
     iters_last = float(out["iters"].double().mean().item())
     rf = rollout_roofline(r5["solver"], r5, torch, np, n, H, dtype)
@@ -986,25 +1098,14 @@ def rollout_bench(args, W, synth, torch, np, dist, world, rank, local_rank):
                 flops_src = {"flops_per_tick": rollout_flops_only(r5, H)}
             except Exception:
                 flops_src = None
-        warm_on = os.environ.get("WBC_ROLLOUT_WARM", "1") != "0"
-        print_line({
-            "metric": "WBC control-steps/sec (batched DogBot)", "value": value,
-            "unit": "control-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": dtype, "data": "synthetic",
-            "config": {"workload": "configs[4]: horizon=%d x batch=%d rollouts per GPU, trot masks, observer on, pushes, %s; "
-                                   "one step = one rollout (%d dependent ticks incl. %sforward dynamics + integrator)"
-                                   % (H, n, dtype, H, "CoM planner/reference generator + " if args.tracking else ""),
-                       "batch_per_gpu": n, "horizon": H, "parallelism": "batch-sharded x%d, rank-local for all ticks" % world,
-                       "qp_warm_start": ("ticks after the first start their QPs from the previous tick's active set (wbc_solver_options.rollout_warm = 1; "
-                                         "results do not depend on it)" if warm_on else "off (rollout_warm = 0): every tick solves from the unconstrained minimum"),
-                       "launches": ("one persistent rollout_kernel launch per rollout" if (n <= 4096 and os.environ.get("WBC_ROLLOUT_PERSISTENT", "1") != "0")
-                                    else "per tick: %sdyn_sweep/fused tick, qp, integrate" % ("reference, " if args.tracking else ""))},
-            "us_per_tick": elapsed / args.steps / H * 1e6, "qp": {"status_ok_frac_last_tick": ok, "iters_mean_last_tick": iters_last},
+        res = contract(elapsed)
+        res.update({
+            "qp": {"status_ok_frac_last_tick": ok, "iters_mean_last_tick": iters_last},
             "timing": {"blocks": len(blocks), "steps_per_block": args.steps, "block_ms_min": min(blocks) * 1e3,
                        "block_ms_median": elapsed * 1e3, "block_ms_max": max(blocks) * 1e3},
             "rccl_ranks": world if dist is not None else None,
             "roofline": rollout_measurement_objects(rf, flops_src, value, n, H, dtype, world), "cpu_baseline": cpu})
+        print_line(res)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -1494,7 +1595,7 @@ def cpu_baseline(B, P, dtype, n):
             "parallel_efficiency": best / (one * bt),
             "sample": "the same %d-state batch, %d passes inside one OpenMP region on %d thread(s) (static schedule, per-thread scratch); ~4 s "
                       "single-thread + ~2.5 s per thread count tried %s; host: %d logical CPUs, %d in the affinity mask, cgroup quota %s cores; "
-                      "OMP_PROC_BIND=%s OMP_PLACES=%s; g++ -O2 -march=native build of oracle/"
+                      "OMP_PROC_BIND=%s OMP_PLACES=%s; g++ -O2 -march=x86-64-v3 build of oracle/"
                       % (n, br, bt, sorted(tried), host["nproc"], host["affinity"],
                          ("%.1f" % host["cgroup_cpu_quota_cores"]) if host["cgroup_cpu_quota_cores"] else "none",
                          os.environ.get("OMP_PROC_BIND"), os.environ.get("OMP_PLACES")),

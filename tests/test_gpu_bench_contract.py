@@ -1,13 +1,17 @@
-"""GPU: `bench.py` keeps the driver's contract -- one JSON line on stdout with the fixed keys, the `roofline` and
-`cpu_baseline` objects, numbers that agree with each other -- when it is started the way the driver starts it
-(`python bench.py --gpus 1 --steps K --warmup W`) and as the one-rank `torch.distributed.run` job of the N > 1 recipe.
+"""GPU: `bench.py` keeps the driver's contract -- one JSON line on stdout with the fixed keys, numbers that agree with each
+other -- when it is started the way the driver starts it (`python bench.py --gpus 1 --steps K --warmup W`: the lean line of
+exactly K timed ticks, and with --dump-outputs the arrays of its last tick) and as the one-rank `torch.distributed.run` job of
+the N > 1 recipe; with --full the line also carries the `roofline` and `cpu_baseline` objects and the extra legs.
 bench.py runs as a CHILD process (it initialises the GPU itself)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from tests.util import relerr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -23,7 +27,7 @@ def one_line(cmd):
     return json.loads(lines[0])
 
 
-def check_common(d, steps, warmup):
+def check_contract(d, steps, warmup):
     assert d["metric"] == "WBC control-steps/sec (batched DogBot)" and d["unit"] == "control-steps/s"
     assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -33,6 +37,10 @@ def check_common(d, steps, warmup):
     # value = states of the K ticks / the time of the K ticks
     assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
     assert 1e7 < d["value"] < 1e9
+
+
+def check_common(d, steps, warmup):
+    check_contract(d, steps, warmup)
     r = d["roofline"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
@@ -44,7 +52,7 @@ def check_common(d, steps, warmup):
 
 
 def test_driver_command_line():
-    d = one_line([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--large-batch", "0", "--no-latency"])
+    d = one_line([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--large-batch", "0", "--no-latency"])
     for k in KEYS:
         assert k in d, k
     check_common(d, 20, 5)
@@ -52,10 +60,61 @@ def test_driver_command_line():
     assert c["kind"] == "port" and c["unit"] == d["unit"] and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
 
 
+def test_plain_line_is_lean_and_dumps_the_last_tick(tmp_path, oracle):
+    """The driver's command without --full: the contract fields only, `steps` = the ticks timed (one block), and --dump-outputs writes
+    the arrays the tick returned -- the same bits whatever the step count (standing inputs, observer off), and the oracle's torques."""
+    import wbc_quadruped_dob_amd as W
+    from wbc_quadruped_dob_amd import synth
+    dumps = []
+    for steps in (30, 7):
+        out = tmp_path / ("s%d" % steps)
+        d = one_line([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "3", "--dump-outputs", str(out)])
+        check_contract(d, steps, 3)
+        assert d["timing"]["blocks"] == 1 and d["timing"]["steps_per_block"] == steps
+        for k in ("roofline", "cpu_baseline", "kernels", "qp", "qp_latency", "closed_loop", "roofline_large_batch", "device"):
+            assert k not in d, k
+        got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+        rows = dict(tau=12, f=12, M=171, h=18, Jc=216, pf=12)
+        assert set(got) == set(rows) | {"status", "iters"}
+        for k, a in got.items():
+            assert a.dtype == np.float64 and a.shape == ((rows[k], 4096) if k in rows else (4096,)), (k, a.dtype, a.shape)
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        dumps.append(got)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    g = dumps[0]
+    assert (g["status"] == 0).all()
+    P = synth.default_params(observer_order=0)
+    m = 256
+    B = synth.make_batch(2, 4096, W.Model.from_urdf(W.SYNTHETIC_URDF).total_mass, rank=0)
+    ref = oracle.step(P, *[B[k][:m] for k in ("q", "v", "w_des", "vdot_des", "normals", "mu", "mask", "tau_prev", "f_prev")], nthreads=8)
+    assert relerr(g["tau"][:, :m].T, ref["tau"]) < 1e-9 and relerr(g["f"][:, :m].T, ref["f"]) < 1e-9
+
+
+def test_plain_rollout_and_single_process_lines_dump_outputs(tmp_path):
+    """--config 5 and --single-process without --full: the contract fields of exactly `steps` timed steps, and the dumps of the last one
+    (the rollout's advanced q, v and observer state beside its outputs; the shards of the single process side by side)."""
+    out5 = tmp_path / "cfg5"
+    d = one_line([sys.executable, "bench.py", "--config", "5", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out5)])
+    assert d["steps"] == 4 and d["timing"]["blocks"] == 1 and "roofline" not in d and "cpu_baseline" not in d
+    assert abs(d["value"] - 20 * 1024 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    g = {f[:-4]: np.load(out5 / f) for f in os.listdir(out5)}
+    assert {"tau", "f", "status", "iters", "q", "v", "obs_integ", "obs_r"} <= set(g)
+    assert g["q"].shape == (19, 1024) and g["obs_r"].shape == (18, 1024) and (g["status"] == 0).all()
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in g.values())
+    outm = tmp_path / "multi"
+    d = one_line([sys.executable, "bench.py", "--gpus", "2", "--single-process", "--batch", "1000", "--steps", "5", "--warmup", "2",
+                  "--dump-outputs", str(outm)])
+    assert d["n_gpus"] == 2 and d["steps"] == 5 and d["timing"]["blocks"] == 1 and "with_tau_allgather" not in d
+    assert abs(d["value"] - 2000 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    g = {f[:-4]: np.load(outm / f) for f in os.listdir(outm)}
+    assert g["tau"].shape == (12, 2000) and (g["status"] == 0).all()
+
+
 def test_one_rank_of_the_multi_gpu_recipe():
     env_port = str(29600 + os.getpid() % 300)
     d = one_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                  "--master-port", env_port, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu",
+                  "--master-port", env_port, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu",
                   "--large-batch", "0", "--no-latency"])
     for k in KEYS[:-1]:
         assert k in d, k
@@ -69,7 +128,7 @@ def test_scale_legs_of_the_multi_gpu_line_on_one_rank():
     env = dict(os.environ, WBC_BENCH_FORCE_DIST="1")
     port = str(29900 + os.getpid() % 90)
     run = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                          "--master-port", port, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu", "--large-batch", "0", "--no-latency"],
+                          "--master-port", port, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--large-batch", "0", "--no-latency"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [l for l in run.stdout.splitlines() if l.strip()]
@@ -97,7 +156,7 @@ def test_scale_legs_of_the_multi_gpu_line_on_one_rank():
 def test_config5_line_carries_roofline_and_cpu_baseline():
     """`bench.py --config 5` (BASELINE.json configs[4]: horizon-20 rollouts of 1 024 robots): both measurement objects, priced on the
     rollout launch's own start / stop events and the oracle's instrumented operation count; the CPU leg is the oracle's rollout()."""
-    d = one_line([sys.executable, "bench.py", "--config", "5", "--steps", "5", "--warmup", "2"])
+    d = one_line([sys.executable, "bench.py", "--config", "5", "--steps", "5", "--warmup", "2", "--full"])
     for k in KEYS:
         assert k in d, k
     assert "configs[4]" in d["config"]["workload"] and d["config"]["batch_per_gpu"] == 1024 and d["config"]["horizon"] == 20
@@ -116,7 +175,7 @@ def test_config5_line_carries_roofline_and_cpu_baseline():
 def test_closed_loop_leg_reports_cold_and_warm_ticks_of_a_drifting_batch():
     """--closed-loop adds the dependent-tick leg BESIDE `value` (which stays the cold tick on standing inputs): same batch, inputs rewritten
     every tick, wbc_step_batch against wbc_step_batch_warm; both loops solve every QP, the warm one in fewer iterations."""
-    d = one_line([sys.executable, "bench.py", "--steps", "50", "--warmup", "5", "--large-batch", "0", "--no-latency", "--no-cpu", "--closed-loop"])
+    d = one_line([sys.executable, "bench.py", "--steps", "50", "--warmup", "5", "--full", "--large-batch", "0", "--no-latency", "--no-cpu", "--closed-loop"])
     check_common(d, 50, 5)
     cl = d["closed_loop"]
     for tag in ("cold", "warm"):

@@ -10,7 +10,7 @@ done
 for rep in 1 2; do for L in "$@"; do
   export WBC_LIB=$PWD/wbc_quadruped_dob_amd/lib/$L
   for args in "--batch 4096" "--config 3 --batch 4096" "--batch 262144 --steps 50 --warmup 5"; do
-    python bench.py --steps 300 --warmup 30 --no-cpu --no-latency --large-batch 0 $args 2>/dev/null | python3 -c "
+    python bench.py --full --steps 300 --warmup 30 --no-cpu --no-latency --large-batch 0 $args 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.read()); k=r['kernels']; f=lambda x:'-' if x is None else '%.1f'%x
 print('$L rep $rep [$args] ms/step %.4f  steps/s %.4e  fused %s dyn %s qp %s'%(r['ms_per_step'],r['value'],f(k.get('fused_tick_us')),f(k['dyn_sweep_us']),f(k['qp_us'])))" >> gpurun_out/ablib.log

@@ -38,5 +38,5 @@ c = d.get("closed_loop")
 if c and "cold" in c: line += "  | closed loop cold %.2f us (kernels %.1f) warm %.2f us (kernels %.1f)" % (c["cold"]["us_per_tick"], c["cold"]["kernels_sum_us"], c["warm"]["us_per_tick"], c["warm"]["kernels_sum_us"])
 print(line)'
 for rep in 1 2 3; do for L in "$@"; do
-  WBC_LIB=$PWD/wbc_quadruped_dob_amd/$L/libwbc_hip.so python bench.py --no-cpu --no-latency --large-batch 0 $args 2>/dev/null | python -c "$pick" "$L [$args] rep $rep"
+  WBC_LIB=$PWD/wbc_quadruped_dob_amd/$L/libwbc_hip.so python bench.py --full --no-cpu --no-latency --large-batch 0 $args 2>/dev/null | python -c "$pick" "$L [$args] rep $rep"
 done; done

@@ -4,7 +4,7 @@
 # of the cause from user space (usage: tools/clock_probe.sh > gpurun_out/clock_probe.log).
 export TMPDIR=/tmp
 R="${GRAFT_REPO_ROOT:-$PWD}"
-python3 "$R/bench.py" --no-cpu --no-latency --large-batch 0 --steps 6000 --warmup 20 --batch 262144 > /tmp/clock_probe_bench.json 2>/dev/null &
+python3 "$R/bench.py" --full --no-cpu --no-latency --large-batch 0 --steps 6000 --warmup 20 --batch 262144 > /tmp/clock_probe_bench.json 2>/dev/null &
 BP=$!
 sleep 2
 for i in $(seq 1 60); do

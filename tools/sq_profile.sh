@@ -11,7 +11,7 @@ P3="SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_V
 P4="SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_MISC SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE"
 for i in $PASSES; do
   eval P=\$P$i
-  rocprofv3 --pmc $P --kernel-trace --output-format csv -d "$OUT" -o p$i -- python3 "$R/bench.py" --steps 6 --warmup 2 --no-cpu --no-latency --large-batch 0 --batch $B ${EXTRA:-} > "$OUT/p$i.log" 2>&1
+  rocprofv3 --pmc $P --kernel-trace --output-format csv -d "$OUT" -o p$i -- python3 "$R/bench.py" --full --steps 6 --warmup 2 --no-cpu --no-latency --large-batch 0 --batch $B ${EXTRA:-} > "$OUT/p$i.log" 2>&1
 done
 python3 - "$OUT" <<'PY'
 import csv,glob,sys,collections,json,os
