@@ -283,6 +283,27 @@ int wbc_integrate_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M
 int wbc_rollout_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
                       const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, void* stream);
 
+/* (ABI 10) Plant model mismatch: rollouts and forward dynamics whose PLANT carries a rigid payload on its trunk (body 0) while the controller
+ * keeps the nominal model -- the case the disturbance observer exists for.  Plant dynamics:
+ *   (M + dM(q)) vdot = S^T tau + Jc^T f + tau_ext - (h + dh(q, v)),   then the semi-implicit Euler step of wbc_integrate_batch.
+ * A body fixed to the trunk changes only the 6x6 base block of M and the 6 base rows of h, so the correction is exact.
+ * M, h, Jc in `out` stay the controller's nominal-model outputs.  plant == NULL or plant->payload == NULL runs exactly the calls without
+ * `plant` (same kernels, same bits).  Stream rules as for those calls: no allocation, no synchronisation, capturable in a hipGraph. */
+#define WBC_PAYLOAD_WORDS 10
+/* payload [10][N], solver scalar type, component-major like every batch array:
+ *   0: m (kg, >= 0)   1..3: c, payload CoM in the BASE frame (m)   4..9: I about c, base axes: xx yy zz xy xz yz (kg m^2)
+ * A row of zeros = no payload for that state.  Values are not checked on the device: m >= 0 and a physical (PSD) inertia are
+ * the caller's promise, as for q / v today. */
+typedef struct wbc_plant {
+  size_t struct_size;    /* sizeof(wbc_plant) of the caller's build */
+  const void* tau_ext;   /* [nv][N] or NULL: as in wbc_integrate_batch / wbc_rollout_batch */
+  const void* payload;   /* [WBC_PAYLOAD_WORDS][N] or NULL */
+} wbc_plant;
+int wbc_integrate_plant_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
+                              const void* tau, const void* f, const wbc_plant* plant, void* stream);
+int wbc_rollout_plant_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                            const wbc_observer_state* obs, const wbc_plant* plant, void* tau_traj, void* stream);
+
 /* SURVEY.md 8(f)-3 -- the caller on the input side of the tick: "a motion planner for the trajectory of the robot's
  * center of mass" (/root/reference/README.md:11) produces the references the whole-body controller tracks.  The
  * planner's source is absent from the reference ([UNVERIFIED] interface); this entry point is the build's definition:
@@ -313,6 +334,10 @@ int wbc_reference_batch(wbc_solver* s, size_t N, const void* q, const void* v, c
 int wbc_rollout_tracking_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
                                const wbc_observer_state* obs, const void* tau_ext, const void* plan, void* tau_traj,
                                void* com_traj, void* stream);
+/* wbc_rollout_tracking_batch with the plant of wbc_rollout_plant_batch (ABI 10) */
+int wbc_rollout_tracking_plant_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                                     const wbc_observer_state* obs, const wbc_plant* plant, const void* plan, void* tau_traj,
+                                     void* com_traj, void* stream);
 
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
@@ -453,7 +478,7 @@ int wbc_qp_dense_batch(int dtype, size_t N, int n, int m, int meq, const void* H
 
 const char* wbc_strerror(int status);
 const char* wbc_last_error(void); /* thread-local detail string of the last failure */
-int wbc_abi_version(void); /* 9 */
+int wbc_abi_version(void); /* 10 */
 
 #ifdef __cplusplus
 }

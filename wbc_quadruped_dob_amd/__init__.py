@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("WBC_LIB") or os.path.join(_HERE, "lib", "libwbc_hip.s
 SYNTHETIC_URDF = os.path.join(_HERE, "assets", "synthetic_quadruped.urdf")
 WBC_MAXV = 32
 F64, F32 = 0, 1
-ABI_VERSION = 9   # include/wbc_hip.h: wbc_abi_version()
+ABI_VERSION = 10   # include/wbc_hip.h: wbc_abi_version()
 
 _lib = None
 
@@ -229,6 +229,9 @@ def lib():
         L.wbc_reference_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 4
         L.wbc_compute_reference.argtypes = [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 3
         L.wbc_rollout_tracking_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 8
+        L.wbc_integrate_plant_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
+        L.wbc_rollout_plant_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 6
+        L.wbc_rollout_tracking_plant_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 8
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -253,6 +256,32 @@ def lib():
 def _check(code, where):
     if code != 0:
         raise WbcError(code, where)
+
+
+PAYLOAD_WORDS = 10   # include/wbc_hip.h: WBC_PAYLOAD_WORDS
+
+
+class Plant(C.Structure):
+    """wbc_plant (ABI 10): what the plant of wbc_*_plant_batch has that the controller's model lacks"""
+    _fields_ = [("struct_size", C.c_size_t), ("tau_ext", C.c_void_p), ("payload", C.c_void_p)]
+
+
+def payload_rows(m, c, I):
+    """The [PAYLOAD_WORDS, N] payload array of the *_plant_batch calls (numpy float64) from per-state values: m [N] (kg), c [N, 3]
+    (payload CoM in the BASE frame, m), I [N, 3, 3] (inertia about c, base axes, kg m^2) or [N, 6] as xx yy zz xy xz yz.
+    Scalars and single rows broadcast over N.  A state with m = 0 and I = 0 carries no payload."""
+    m = np.atleast_1d(np.asarray(m, dtype=np.float64))
+    c = np.atleast_2d(np.asarray(c, dtype=np.float64))
+    I = np.asarray(I, dtype=np.float64)
+    if I.shape[-2:] == (3, 3):
+        I = np.stack([I[..., 0, 0], I[..., 1, 1], I[..., 2, 2], I[..., 0, 1], I[..., 0, 2], I[..., 1, 2]], axis=-1)
+    I = np.atleast_2d(I)
+    N = max(len(m), len(c), len(I))
+    out = np.empty((PAYLOAD_WORDS, N))
+    out[0] = np.broadcast_to(m, (N,))
+    out[1:4] = np.broadcast_to(c, (N, 3)).T
+    out[4:10] = np.broadcast_to(I, (N, 6)).T
+    return out
 
 
 class Model:
@@ -448,19 +477,42 @@ class Solver:
         """keep_structural: the next tick writes M / Jc in full again (their buffers were freed, reallocated or overwritten)."""
         _check(lib().wbc_solver_invalidate_structural(self._h), "wbc_solver_invalidate_structural")
 
-    def integrate(self, q, v, M, h, Jc, tau, f, tau_ext=None):
-        """Forward dynamics with the planned GRFs + semi-implicit Euler; q, v advance IN PLACE (one dt)."""
+    def _plant(self, tau_ext, payload, N):
+        """wbc_plant for the *_plant_batch calls (payload [PAYLOAD_WORDS, N]: a device tensor of the solver's dtype, or the numpy array of
+        payload_rows, copied to the device here)"""
+        if isinstance(payload, np.ndarray):
+            payload = self.torch.from_numpy(np.ascontiguousarray(payload)).to(device=self.device, dtype=self.tdtype)
+        pl = Plant()
+        pl.struct_size = C.sizeof(Plant)
+        pl.tau_ext = self._ptr(tau_ext, self.model.nv, N)
+        pl.payload = self._ptr(payload, PAYLOAD_WORDS, N)
+        pl._keep = payload   # (the caching allocator reuses its memory only behind this call's work on the stream)
+        return pl
+
+    def integrate(self, q, v, M, h, Jc, tau, f, tau_ext=None, payload=None):
+        """Forward dynamics with the planned GRFs + semi-implicit Euler; q, v advance IN PLACE (one dt).
+        payload [PAYLOAD_WORDS, N] (optional, see payload_rows): the PLANT carries it on its trunk (wbc_integrate_plant_batch); M, h, Jc
+        stay the nominal model's."""
         m = self.model
         N = q.shape[1]
+        if payload is not None:
+            pl = self._plant(tau_ext, payload, N)
+            _check(lib().wbc_integrate_plant_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
+                                                   self._ptr(M, m.nv * (m.nv + 1) // 2, N), self._ptr(h, m.nv, N),
+                                                   self._ptr(Jc, 3 * m.nf * m.nv, N), self._ptr(tau, m.nj, N), self._ptr(f, 3 * m.nf, N),
+                                                   C.byref(pl), self._stream()), "wbc_integrate_plant_batch")
+            return
         _check(lib().wbc_integrate_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
                                          self._ptr(M, m.nv * (m.nv + 1) // 2, N), self._ptr(h, m.nv, N),
                                          self._ptr(Jc, 3 * m.nf * m.nv, N), self._ptr(tau, m.nj, N), self._ptr(f, 3 * m.nf, N), self._ptr(tau_ext, m.nv, N),
                                          self._stream()), "wbc_integrate_batch")
 
     def rollout(self, horizon, q, v, w_des, vdot_des, normals, mu, mask, out, obs_integ=None, obs_r=None, tau_ext=None,
-                tau_traj=None):
+                tau_traj=None, payload=None):
         """`horizon` dependent ticks; q, v advance IN PLACE; `out` must hold tau, f (previous outputs or zeros), status,
-        iters, M, h, Jc (e.g. the dict a previous step(..., want_mats=True) returned)."""
+        iters, M, h, Jc (e.g. the dict a previous step(..., want_mats=True) returned).
+        payload [PAYLOAD_WORDS, N] (optional, see payload_rows): the PLANT carries it on its trunk, the controller keeps the nominal model
+        (wbc_rollout_plant_batch)."""
         torch = self.torch
         m = self.model
         N = q.shape[1]
@@ -475,6 +527,11 @@ class Solver:
         if tau_traj is not None:
             assert tau_traj.is_cuda and tau_traj.is_contiguous() and tau_traj.numel() == horizon * m.nj * N
             tt = C.c_void_p(tau_traj.data_ptr())
+        if payload is not None:
+            pl = self._plant(tau_ext, payload, N)
+            _check(lib().wbc_rollout_plant_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob), C.byref(pl), tt,
+                                                 self._stream()), "wbc_rollout_plant_batch")
+            return out
         _check(lib().wbc_rollout_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob),
                                        self._ptr(tau_ext, m.nv, N), tt, self._stream()), "wbc_rollout_batch")
         return out
@@ -502,8 +559,9 @@ class Solver:
         return out
 
     def rollout_tracking(self, horizon, q, v, plan, normals, mu, mask, out, w_des, vdot_des, obs_integ=None, obs_r=None,
-                         tau_ext=None, tau_traj=None, com_traj=None):
-        """rollout() with the planner in the loop: w_des / vdot_des are scratch buffers regenerated every tick."""
+                         tau_ext=None, tau_traj=None, com_traj=None, payload=None):
+        """rollout() with the planner in the loop: w_des / vdot_des are scratch buffers regenerated every tick.
+        payload: as in rollout() (wbc_rollout_tracking_plant_batch)."""
         torch = self.torch
         m = self.model
         N = q.shape[1]
@@ -521,6 +579,12 @@ class Solver:
         if com_traj is not None:
             assert com_traj.is_cuda and com_traj.is_contiguous() and com_traj.numel() == horizon * 6 * N
             ct = C.c_void_p(com_traj.data_ptr())
+        if payload is not None:
+            pl = self._plant(tau_ext, payload, N)
+            _check(lib().wbc_rollout_tracking_plant_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob), C.byref(pl),
+                                                          self._ptr(plan, PLAN_WORDS, N), tt, ct, self._stream()),
+                   "wbc_rollout_tracking_plant_batch")
+            return out
         _check(lib().wbc_rollout_tracking_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob),
                                                 self._ptr(tau_ext, m.nv, N), self._ptr(plan, PLAN_WORDS, N), tt, ct,
                                                 self._stream()), "wbc_rollout_tracking_batch")

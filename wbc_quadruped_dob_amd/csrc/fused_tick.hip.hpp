@@ -242,9 +242,11 @@ __host__ __device__ constexpr int rollout_threads(bool observer, int spw) {
        : (spw == 16) ? (observer ? 512 : 384)   // QP x 4, rnea, mass_jac [, observer base rows, joint rows]: no integrator wavefront
        : (observer ? 512 : 448);
 }
-template <class T, bool OBSERVER, bool TRACK, int SPW = 16, bool WARM = false>
+// PAYLOAD: the plant carries a payload on its trunk (integrate.hip.hpp, PAYLOAD: phase 1 on the mass_jac wavefront, phase 2 on wavefront 0; the controller's
+// roles keep the nominal model); `ia` is then a PlantIntegrateArgs.  false: the kernels of round 6, argument layout and code unchanged.
+template <class T, bool OBSERVER, bool TRACK, int SPW = 16, bool WARM = false, bool PAYLOAD = false>
 __global__ __launch_bounds__(rollout_threads(OBSERVER, SPW), 1) void rollout_kernel(const DevModel<T>* __restrict__ model, DevParams<T> prm,
-                                                                         SweepArgs<T> a, QpArgs<T> qa, QpJidx jmap, IntegrateArgs<T> ia,
+                                                                         SweepArgs<T> a, QpArgs<T> qa, QpJidx jmap, IntegrateArgsP<T, PAYLOAD> ia,
                                                                          int horizon, const DevRefParams<T>* __restrict__ G, RefArgs<T> ra) {
   __shared__ __attribute__((aligned(512))) T cst[CST_WORDS];   // (the alignment puts the table FIRST in the workgroup's LDS: within reach of the 16-bit ds_read offset, see dyn_sweep.hip.hpp)
   __shared__ int zidx_s[64];
@@ -277,6 +279,8 @@ __global__ __launch_bounds__(rollout_threads(OBSERVER, SPW), 1) void rollout_ker
                                                                                          // publishes only after it has waited for these references)
   T* const traj0 = ia.tau_traj;
   T* const com0 = ra.com;
+  const T* payload = nullptr;   // (PAYLOAD) [10][N], read by both phases of the integrator every tick (L2-resident)
+  if constexpr (PAYLOAD) payload = ia.payload;
   // (WARM) the active set of each of the workgroup's states, from tick to tick: one LDS word per state, read and written by the state's own
   // QP row only (a register of the QP wavefronts would be live through every role's code of this 256-register kernel)
   __shared__ int aset_sh[16];
@@ -444,7 +448,8 @@ __global__ __launch_bounds__(rollout_threads(OBSERVER, SPW), 1) void rollout_ker
         RSTAMP(1);   // (WBC_RO_STAMP_ALT) mass_jac: image published
         // phase 1 of the integrator, on my own image (my own LDS words: program order of one lane); the factors are complete when this wavefront
         // reaches the tick barrier, behind which the integrator wavefront reads them
-        integrate_body<T, SPW, IntegrateNoWait, 1, true, true, false, IntegrateNoWait, true>(model, ia1, IntegrateNoWait(), handp, nullptr, factp);
+        integrate_body<T, SPW, IntegrateNoWait, 1, true, true, false, IntegrateNoWait, true, PAYLOAD>(model, ia1, IntegrateNoWait(), handp, nullptr, factp,
+                                                                                                       IntegrateNoWait(), payload);
            // the factors are in LDS: wavefront 0 may start phase 2
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
           if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(fflag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -515,7 +520,8 @@ __global__ __launch_bounds__(rollout_threads(OBSERVER, SPW), 1) void rollout_ker
           RSTAMP(7);   // phase 2 starts (the factors are there)
 #endif
 // 1: the tick's barrier in FRONT of this wavefront's stores (integrate.hip.hpp, after_state: measured, not kept)
-                      integrate_body<T, SPW, IntegrateNoWait, 2, true, true, true, IntegrateNoWait, true>(model, iat, IntegrateNoWait(), mj_hand, res_img, fact_sh);
+                      integrate_body<T, SPW, IntegrateNoWait, 2, true, true, true, IntegrateNoWait, true, PAYLOAD>(model, iat, IntegrateNoWait(), mj_hand, res_img,
+                                                                                                                   fact_sh, IntegrateNoWait(), payload);
             RSTAMP(8);
           
         }

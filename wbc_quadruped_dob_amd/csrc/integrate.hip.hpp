@@ -16,6 +16,53 @@
 
 namespace wbc {
 
+// ---- plant payload (wbc_integrate_plant_batch, wbc_rollout_plant_batch, wbc_rollout_tracking_plant_batch)
+// A rigid body fixed to the trunk: p = [m, c (3, base frame), I about c (6, base axes: xx yy zz xy xz yz)], [PAYLOAD_WORDS][N] in memory.
+// It moves with the base and with no joint, so it changes only the 6x6 base block of M and the 6 base rows of h -- exactly.  In the mixed
+// representation (v = [pdot world, omega world, qdot]; base rows = force in world, moment about the base origin in world), with r = R c,
+// I_w = R I R^T and g the model's gravity:
+//   dM_bb = [[m 1, -m[r]x], [m[r]x, I_w - m[r]x[r]x]]
+//   dh_b  = [f; r x f + w x (I_w w)],   f = m w x (w x r) - m g
+// dM: upper triangle of the 6x6 block, row-major (21 words); dh: 6 words.  Unused outputs cost nothing (the body is inlined).
+constexpr int PAYLOAD_WORDS = 10;
+template <class T>
+WBC_DEV void payload_terms(const T (&R)[9], V3<T> om, const T (&p)[PAYLOAD_WORDS], const T* __restrict__ grav, T (&dM)[21], T (&dh)[6]) {
+  const T m = p[0];
+  const V3<T> r = mk<T>(R[0] * p[1] + R[1] * p[2] + R[2] * p[3], R[3] * p[1] + R[4] * p[2] + R[5] * p[3], R[6] * p[1] + R[7] * p[2] + R[8] * p[3]);
+  // I_w = R I R^T: B = R I (I symmetric), then I_w[i][j] = B[i] . R[j]
+  const T Ib[9] = {p[4], p[7], p[8], p[7], p[5], p[9], p[8], p[9], p[6]};
+  T B[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) B[3 * i + j] = R[3 * i] * Ib[j] + R[3 * i + 1] * Ib[3 + j] + R[3 * i + 2] * Ib[6 + j];
+  auto iw = [&](int i, int j) { return B[3 * i] * R[3 * j] + B[3 * i + 1] * R[3 * j + 1] + B[3 * i + 2] * R[3 * j + 2]; };
+  const T Wxx = iw(0, 0), Wxy = iw(0, 1), Wxz = iw(0, 2), Wyy = iw(1, 1), Wyz = iw(1, 2), Wzz = iw(2, 2);
+  const V3<T> h = r * m;   // first moment about the base origin
+  const T Z = (T)0;
+  // rows 0 .. 2: [m 1, -[h]x]
+  dM[0] = m; dM[1] = Z; dM[2] = Z; dM[3] = Z;    dM[4] = h.z;  dM[5] = -h.y;
+  dM[6] = m; dM[7] = Z; dM[8] = -h.z;            dM[9] = Z;    dM[10] = h.x;
+  dM[11] = m; dM[12] = h.y; dM[13] = -h.x;       dM[14] = Z;
+  // rows 3 .. 5: I_w - m[r]x[r]x = I_w + m (|r|^2 1 - r r^T)
+  dM[15] = Wxx + (h.y * r.y + h.z * r.z); dM[16] = Wxy - h.x * r.y; dM[17] = Wxz - h.x * r.z;
+  dM[18] = Wyy + (h.x * r.x + h.z * r.z); dM[19] = Wyz - h.y * r.z;
+  dM[20] = Wzz + (h.x * r.x + h.y * r.y);
+  const V3<T> f = cross(om, cross(om, r)) * m - mk<T>(grav[0], grav[1], grav[2]) * m;
+  const V3<T> Lw = mk<T>(Wxx * om.x + Wxy * om.y + Wxz * om.z, Wxy * om.x + Wyy * om.y + Wyz * om.z, Wxz * om.x + Wyz * om.y + Wzz * om.z);
+  const V3<T> n = cross(r, f) + cross(om, Lw);
+  dh[0] = f.x; dh[1] = f.y; dh[2] = f.z; dh[3] = n.x; dh[4] = n.y; dh[5] = n.z;
+}
+// R of a unit quaternion (x, y, z, w), row-major (as MAKE_R, dyn_sweep.hip.hpp)
+template <class T> WBC_DEV void quat_to_R(T x, T y, T z, T w, T (&R)[9]) {
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w);     R[2] = 2 * (x * z + y * w);
+  R[3] = 2 * (x * y + z * w);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+  R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
+}
+// the argument struct of the payload kernels: IntegrateArgs + the payload (the kernels without it keep their argument layout)
+template <class T> struct PlantIntegrateArgs : IntegrateArgs<T> { const T* payload; };
+template <class T, bool PAYLOAD> using IntegrateArgsP = typename std::conditional<PAYLOAD, PlantIntegrateArgs<T>, IntegrateArgs<T>>::type;
+
 // (also called as one wavefront of the persistent rollout kernel, fused_tick.hip.hpp: same mapping, no LDS.)
 // Two phases.  Phase 1 needs only M and Jc: the leg blocks' inverses, the base Schur complement and its Cholesky factor.
 // `between()` runs after it (nothing in the stand-alone kernel; the tick barrier in the rollout kernel, where phase 1
@@ -45,10 +92,12 @@ constexpr int INT_FACT_WORDS = 27;
 // can put the tick's barrier there, so that the next tick's roles start while this wavefront (the next tick's QP, idle until the lever arms are out)
 // still issues its stores.  Measured (profiles/r05q_ab_rollout_early_barrier.log): 9.39-9.47 -> 9.48-9.52 us per tick at 1 024 robots, cold 15.71 -> 15.97:
 // not kept (-DWBC_RO_EARLY_BARRIER=1).
+// PAYLOAD (plant model mismatch, `payload` = [PAYLOAD_WORDS][N]): phase 1 adds dM_bb to the base block (with HAND: one more body in the composite
+// (m, R h, R I R^T) before the block is rebuilt), phase 2 subtracts dh_b from the base right-hand side.  false: the code of rounds 1-6, unchanged.
 template <class T, int SPW = 16, class Between = IntegrateNoWait, int PHASE = 0, bool UNGUARD = false, bool HAND = false, bool RESI = false,
-          class AfterState = IntegrateNoWait, bool SIMG_ = false>
+          class AfterState = IntegrateNoWait, bool SIMG_ = false, bool PAYLOAD = false>
 WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const IntegrateArgs<T>& a, Between between = Between(), const T* hand_ = nullptr,
-                            const T* res_ = nullptr, T* fact = nullptr, AfterState after_state = AfterState()) {
+                            const T* res_ = nullptr, T* fact = nullptr, AfterState after_state = AfterState(), const T* payload = nullptr) {
   static_assert(PHASE == 0 || PHASE == 1 || PHASE == 2, "phase");
   static_assert(PHASE == 0 || HAND, "the split phases hand M's blocks over in LDS");
   constexpr bool FASTR = PHASE != 0 && SIMG_;   // (rollout workgroups with the state image) rsqrt_fast, see dyn_sweep.hip.hpp
@@ -101,6 +150,8 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
 #pragma unroll
       for (int k = 0; k < 3; ++k) Mb[r][k] = HAND ? hl[(6 + 3 * r + k) * 64] : LDV(a.M, midx18(r, r) + (6 + jx[k] - r));
   };
+  T dhp[6];   // (PAYLOAD) dh_b; the stand-alone kernel (PHASE 0) forms it in phase 1 beside dM_bb from the same loads and rotation (one payload_terms
+              // per state, not one per phase); the split phases of the persistent rollout form it in phase 2
   if constexpr (PHASE != 2) {
   load_blocks();
   // leg block (symmetric 3x3) of M
@@ -115,18 +166,46 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
     }
   // base block of M (upper triangle): from the buffer, or rebuilt from (m, R h, R I R^T) of the hand-over image
   T Mbb[6][6];
-  if constexpr (HAND) {
-    const T tm = hl[36 * 64], hx = hl[37 * 64], hy = hl[38 * 64], hz = hl[39 * 64];
-    const T Z = (T)0;
-    Mbb[0][0] = tm; Mbb[0][1] = Z; Mbb[0][2] = Z; Mbb[0][3] = Z; Mbb[0][4] = hz; Mbb[0][5] = -hy;
-    Mbb[1][1] = tm; Mbb[1][2] = Z; Mbb[1][3] = -hz; Mbb[1][4] = Z; Mbb[1][5] = hx;
-    Mbb[2][2] = tm; Mbb[2][3] = hy; Mbb[2][4] = -hx; Mbb[2][5] = Z;
-    Mbb[3][3] = hl[40 * 64]; Mbb[3][4] = hl[41 * 64]; Mbb[3][5] = hl[42 * 64]; Mbb[4][4] = hl[43 * 64]; Mbb[4][5] = hl[44 * 64]; Mbb[5][5] = hl[45 * 64];
-  } else {
+  if constexpr (!HAND) {
 #pragma unroll
     for (int r = 0; r < 6; ++r)
 #pragma unroll
       for (int c = r; c < 6; ++c) Mbb[r][c] = LDU(a.M, midx18(r, c));
+  }
+  // (PAYLOAD) the payload's share of the base block, dM_bb, from the state's attitude: the unit quaternion from the state image (persistent rollout)
+  // or from memory, the payload's 10 words from memory (L2: the whole array is 80 bytes per state)
+  T dM[21];
+  if constexpr (PAYLOAD) {
+    T pw[PAYLOAD_WORDS];
+#pragma unroll
+    for (int k = 0; k < PAYLOAD_WORDS; ++k) pw[k] = LDU(payload, k);
+    const T* const sq = SIMG_ ? a.simg + (int)(s32 - (unsigned)((size_t)blockIdx.x * SPW)) : nullptr;
+    T qx, qy, qz, qw;
+    if constexpr (SIMG_) { qx = sq[3 * 16]; qy = sq[4 * 16]; qz = sq[5 * 16]; qw = sq[6 * 16]; }
+    else { qx = LDU(a.q, 3); qy = LDU(a.q, 4); qz = LDU(a.q, 5); qw = LDU(a.q, 6); }
+    const T n = rsqrt_sel<FASTR>(qx * qx + qy * qy + qz * qz + qw * qw);
+    T R[9], dh[6];
+    quat_to_R<T>(qx * n, qy * n, qz * n, qw * n, R);
+    const V3<T> om = PHASE == 0 ? mk<T>(LDU(a.v, 3), LDU(a.v, 4), LDU(a.v, 5)) : mk<T>((T)0, (T)0, (T)0);
+    payload_terms<T>(R, om, pw, model->grav, dM, PHASE == 0 ? dhp : dh);
+  }
+  if constexpr (HAND) {
+    T tm = hl[36 * 64], hx = hl[37 * 64], hy = hl[38 * 64], hz = hl[39 * 64];
+    T I33 = hl[40 * 64], I34 = hl[41 * 64], I35 = hl[42 * 64], I44 = hl[43 * 64], I45 = hl[44 * 64], I55 = hl[45 * 64];
+    if constexpr (PAYLOAD) {   // one more rigid body in the composite (m, R h, R I R^T)
+      tm += dM[0]; hx += dM[10]; hy += dM[12]; hz += dM[4];
+      I33 += dM[15]; I34 += dM[16]; I35 += dM[17]; I44 += dM[18]; I45 += dM[19]; I55 += dM[20];
+    }
+    const T Z = (T)0;
+    Mbb[0][0] = tm; Mbb[0][1] = Z; Mbb[0][2] = Z; Mbb[0][3] = Z; Mbb[0][4] = hz; Mbb[0][5] = -hy;
+    Mbb[1][1] = tm; Mbb[1][2] = Z; Mbb[1][3] = -hz; Mbb[1][4] = Z; Mbb[1][5] = hx;
+    Mbb[2][2] = tm; Mbb[2][3] = hy; Mbb[2][4] = -hx; Mbb[2][5] = Z;
+    Mbb[3][3] = I33; Mbb[3][4] = I34; Mbb[3][5] = I35; Mbb[4][4] = I44; Mbb[4][5] = I45; Mbb[5][5] = I55;
+  } else if constexpr (PAYLOAD) {
+#pragma unroll
+    for (int r = 0, i = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = r; c < 6; ++c, ++i) Mbb[r][c] += dM[i];
   }
   ISTAMP(1);   // image read requested
   // A = Ml^-1 by cofactors (SPD 3x3)
@@ -249,7 +328,15 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
     rl[k] = taul[k] + jcl[0][k] * fl.x + jcl[1][k] * fl.y + jcl[2][k] * fl.z - hl_k + text(6 + jx[k]);
   }
   ISTAMP(6);   // tau, f, h arrived: leg right-hand side
-  // ---- base right-hand side rb = rhs_b - sum_legs W rl
+  // ---- base right-hand side rb = rhs_b - sum_legs W rl  (PAYLOAD: - dh_b at the state's attitude and angular velocity)
+  if constexpr (PAYLOAD && PHASE != 0) {
+    T pw2[PAYLOAD_WORDS];
+#pragma unroll
+    for (int k = 0; k < PAYLOAD_WORDS; ++k) pw2[k] = LDU(payload, k);
+    T R[9], dMp[21];
+    quat_to_R<T>(ux, uy, uz, uw, R);
+    payload_terms<T>(R, mk<T>(vb0[3], vb0[4], vb0[5]), pw2, model->grav, dMp, dhp);
+  }
   T rb[6];
   {
     const V3<T> mo = cross(dl, fl);
@@ -268,6 +355,7 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
         part = own[r] - (Wr[0] * rl[0] + Wr[1] * rl[1] + Wr[2] * rl[2]);
       }
       rb[r] = xrow_sum(part) - (RESI ? rs[(24 + r) * 16] : LDU(a.h, r)) + text(r);
+      if constexpr (PAYLOAD) rb[r] -= dhp[r];
     }
   }
   ISTAMP(7);   // base right-hand side summed
@@ -397,9 +485,16 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
 #undef LDU
 }
 
-template <class T>
-__global__ __launch_bounds__(64) void integrate_kernel(const DevModel<T>* __restrict__ model, IntegrateArgs<T> a) {
-  integrate_body<T>(model, a);
+// PAYLOAD: the plant carries a payload on its trunk (wbc_integrate_plant_batch, and the per-tick launches of the plant rollouts)
+// (fp32: 195 registers with the payload against 160 without -- two wavefronts per SIMD instead of three.  Held to three (amdgpu_waves_per_eu) it
+//  spills 53 scratch instructions; measured cost of the two: DESIGN.md 4.7)
+template <class T, bool PAYLOAD = false>
+__global__ __launch_bounds__(64) void integrate_kernel(const DevModel<T>* __restrict__ model, IntegrateArgsP<T, PAYLOAD> a) {
+  if constexpr (PAYLOAD)
+    integrate_body<T, 16, IntegrateNoWait, 0, false, false, false, IntegrateNoWait, false, true>(model, a, IntegrateNoWait(), nullptr, nullptr, nullptr,
+                                                                                                 IntegrateNoWait(), a.payload);
+  else
+    integrate_body<T>(model, a);
 }
 
 }  // namespace wbc

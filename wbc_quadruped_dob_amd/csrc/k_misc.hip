@@ -18,6 +18,7 @@ hipError_t k_observer<Scalar>(const LaunchCtx& L, const DevModel<Scalar>* model,
   return hipGetLastError();
 }
 
+// (its payload sibling, integrate_kernel<T, true> behind k_integrate_plant, is compiled in the payload unit of k_rollout.hip: -DWBC_ROLLOUT_PAYLOAD=1)
 template <>
 hipError_t k_integrate<Scalar>(const LaunchCtx& L, const DevModel<Scalar>* model, const IntegrateArgs<Scalar>& a) {
   WBC_KLAUNCH(L, (integrate_kernel<Scalar>), dim3((unsigned)((a.N + 15) / 16)), dim3(64), model, a);

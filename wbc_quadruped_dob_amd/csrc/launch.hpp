@@ -81,10 +81,11 @@ template <class T> hipError_t k_fused_tick(const LaunchCtx& L, bool observer, bo
 //  4 352: 20.0 / 18.5, 5 000: 21.3 / 19.6, 6 000: 24.4 / 20.5, 7 500: 24.4 / 20.3, 8 191: 27.4 / 21.1 -- profiles/r06y3_ab_fused_pair_ragged.log)
 constexpr long long WBC_FUSED_PAIR_MIN = 4225, WBC_FUSED_PAIR_MAX = 8192, WBC_FUSED_PAIR_MAX_F32 = 16384;
 template <class T> hipError_t k_fused_pair(const LaunchCtx& L, const DevModel<T>* model, const DevParams<T>& prm, const SweepArgs<T>& a, const QpArgs<T>& qa, const QpJidx& jmap);
-// rollout_kernel<T, OBSERVER, TRACK, SPW>: `horizon` dependent ticks incl. forward dynamics (and the planner) as one launch
+// rollout_kernel<T, OBSERVER, TRACK, SPW, WARM, PAYLOAD>: `horizon` dependent ticks incl. forward dynamics (and the planner) as one launch;
+// payload (non-null, [10][N]): the PAYLOAD instantiations, the plant carries it on its trunk (units k_rollout_pl, k_rollout_track_pl)
 template <class T> hipError_t k_rollout(const LaunchCtx& L, bool observer, bool track, int spw, const DevModel<T>* model, const DevParams<T>& prm,
                                        const SweepArgs<T>& a, const QpArgs<T>& qa, const QpJidx& jmap, const IntegrateArgs<T>& ia, int horizon,
-                                       const DevRefParams<T>* G, const RefArgs<T>& ra, bool warm = false);
+                                       const DevRefParams<T>* G, const RefArgs<T>& ra, bool warm = false, const T* payload = nullptr);
 // qp_general_kernel<T>: dense QPs of run-time size (n <= 36 variables, m <= 64 rows, the first meq of them equalities), one per wavefront
 template <class T> hipError_t k_qp_general(const LaunchCtx& L, const QpGeneralArgs<T>& a);
 // one thread: *ptr = value, system scope (the completion ticket of the flag-polled single-robot tick)
@@ -92,6 +93,8 @@ hipError_t k_flag(hipStream_t st, unsigned* ptr, unsigned value);
 // the peer gather of wbc_multi_*: ONE launch copies `bytes` bytes at src to each of the nd <= 64 destinations (this device's or peer-mapped memory)
 hipError_t k_gather_push(hipStream_t st, const void* src, void* const* dst, int nd, size_t bytes);
 template <class T> hipError_t k_integrate(const LaunchCtx& L, const DevModel<T>* model, const IntegrateArgs<T>& a);
+// integrate_kernel<T, true>: k_integrate with a payload [10][N] on the plant's trunk (integrate.hip.hpp, PAYLOAD; defined in the payload unit of k_rollout.hip)
+template <class T> hipError_t k_integrate_plant(const LaunchCtx& L, const DevModel<T>* model, const IntegrateArgs<T>& a, const T* payload);
 template <class T> hipError_t k_reference(const LaunchCtx& L, const DevModel<T>* model, const DevRefParams<T>* G, const RefArgs<T>& a);
 
 }  // namespace wbc

@@ -1031,7 +1031,7 @@ extern "C" int wbc_step_batch_warm(wbc_solver* s, size_t N, const wbc_batch_in* 
 
 template <class T>
 static int integrate_impl(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
-                          const void* tau, const void* f, const void* tau_ext, void* tau_traj, hipStream_t st) {
+                          const void* tau, const void* f, const void* tau_ext, void* tau_traj, hipStream_t st, const void* payload = nullptr) {
   IntegrateArgs<T> a;
   std::memset(&a, 0, sizeof(a));
   a.N = N; a.q = (T*)q; a.v = (T*)v; a.M = (const T*)M; a.h = (const T*)h; a.Jc = (const T*)Jc;
@@ -1039,7 +1039,7 @@ static int integrate_impl(wbc_solver* s, size_t N, void* q, void* v, const void*
   a.dt = (T)s->params.dt;
   a.jpack = s->jpack;
   LaunchCtx L; L.st = st;
-  hipError_t e = k_integrate<T>(L, dev_model<T>(s), a);
+  hipError_t e = payload ? k_integrate_plant<T>(L, dev_model<T>(s), a, (const T*)payload) : k_integrate<T>(L, dev_model<T>(s), a);
   if (e != hipSuccess) return fail(WBC_E_HIP, std::string("integrate launch: ") + hipGetErrorString(e));
   return WBC_OK;
 }
@@ -1055,11 +1055,35 @@ extern "C" int wbc_integrate_batch(wbc_solver* s, size_t N, void* q, void* v, co
                              : integrate_impl<float>(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, st);
 }
 
+// (ABI 10) the plant's extras of wbc_*_plant_batch: NULL plant = the calls without it; a struct of an older, smaller build is refused
+static int plant_args(const wbc_plant* plant, const void** tau_ext, const void** payload) {
+  *tau_ext = nullptr; *payload = nullptr;
+  if (!plant) return WBC_OK;
+  if (plant->struct_size < sizeof(wbc_plant)) return fail(WBC_E_INVALID, "wbc_plant: struct_size too small");
+  *tau_ext = plant->tau_ext; *payload = plant->payload;
+  return WBC_OK;
+}
+
+extern "C" int wbc_integrate_plant_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
+                                         const void* tau, const void* f, const wbc_plant* plant, void* stream) {
+  const void *tau_ext, *payload;
+  const int rc = plant_args(plant, &tau_ext, &payload);
+  if (rc) return rc;
+  if (!payload) return wbc_integrate_batch(s, N, q, v, M, h, Jc, tau, f, tau_ext, stream);
+  if (!s || !q || !v || !M || !h || !Jc || !tau || !f) return fail(WBC_E_INVALID, "null argument");
+  if (N == 0) return WBC_OK;
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64 ? integrate_impl<double>(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, st, payload)
+                             : integrate_impl<float>(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, st, payload);
+}
+
 // small batches: the whole horizon in ONE launch (rollout_kernel, fused_tick.hip.hpp)
 template <class T>
 static int rollout_persistent(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
                               const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, hipStream_t st,
-                              const void* plan = nullptr, void* com_traj = nullptr) {
+                              const void* plan = nullptr, void* com_traj = nullptr, const void* payload = nullptr) {
   SweepArgs<T> a;
   std::memset(&a, 0, sizeof(a));
   a.jpack = s->jpack;
@@ -1094,14 +1118,15 @@ static int rollout_persistent(wbc_solver* s, size_t N, int horizon, const wbc_ba
   ra.w_des = (T*)in->w_des; ra.vdot_des = (T*)in->vdot_des; ra.com = (T*)com_traj;
   timing_tick(s);
   TIMED_LAUNCH(5, st, "rollout", k_rollout<T>(L, s->params.observer_order > 0, plan != nullptr, spw, dev_model<T>(s), to_dev_params<T>(s->params), a, qa,
-                                              s->jmap, ia, horizon, (const DevRefParams<T>*)s->d_ref, ra, s->opt.rollout_warm != 0));
+                                              s->jmap, ia, horizon, (const DevRefParams<T>*)s->d_ref, ra, s->opt.rollout_warm != 0, (const T*)payload));
   return WBC_OK;
 }
 
 static bool rollout_as_one_launch(const wbc_solver* s, size_t N) { return N <= s->rz.fused_max && s->opt.rollout_persistent; }
 
-extern "C" int wbc_rollout_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
-                                 const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, void* stream) {
+// wbc_rollout_batch; payload (wbc_rollout_plant_batch): the plant's trunk carries it, in the persistent kernel and in the per-tick integrate launches alike
+static int rollout_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                        const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, void* stream, const void* payload) {
   if (!s || !in || !out) return fail(WBC_E_INVALID, "null argument");
   if (horizon < 1) return fail(WBC_E_INVALID, "horizon must be >= 1");
   if (!out->M || !out->h || !out->Jc) return fail(WBC_E_INVALID, "rollouts need the M, h, Jc buffers (forward dynamics reads them)");
@@ -1115,8 +1140,8 @@ extern "C" int wbc_rollout_batch(wbc_solver* s, size_t N, int horizon, const wbc
       return fail(WBC_E_INVALID, "observer on: observer state buffers required");
     ON_DEVICE(s);
     hipStream_t st0 = (hipStream_t)stream;
-    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0)
-                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0);
+    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, nullptr, nullptr, payload)
+                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, nullptr, nullptr, payload);
   }
   wbc_batch_in tick = *in;
   tick.tau_prev = out->tau;  // the previous tick's outputs are this tick's tau_prev / f_prev: the sweep reads them
@@ -1138,11 +1163,24 @@ extern "C" int wbc_rollout_batch(wbc_solver* s, size_t N, int horizon, const wbc
     void* traj = tau_traj ? (void*)((char*)tau_traj + (size_t)t * nj * N * ts) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     rc = s->dtype == WBC_F64
-             ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st)
-             : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st);
+             ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload)
+             : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload);
     if (rc) return rc;
   }
   return WBC_OK;
+}
+
+extern "C" int wbc_rollout_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                                 const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, void* stream) {
+  return rollout_impl(s, N, horizon, in, out, obs, tau_ext, tau_traj, stream, nullptr);
+}
+
+extern "C" int wbc_rollout_plant_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                                       const wbc_observer_state* obs, const wbc_plant* plant, void* tau_traj, void* stream) {
+  const void *tau_ext, *payload;
+  const int rc = plant_args(plant, &tau_ext, &payload);
+  if (rc) return rc;
+  return rollout_impl(s, N, horizon, in, out, obs, tau_ext, tau_traj, stream, payload);
 }
 
 // ------------------------------------------------------------------------------------------ CoM reference generator
@@ -1202,9 +1240,9 @@ extern "C" int wbc_reference_batch(wbc_solver* s, size_t N, const void* q, const
                              : reference_impl<float>(s, N, q, v, plan, t, w_des, vdot_des, com, st);
 }
 
-extern "C" int wbc_rollout_tracking_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in,
-                                          const wbc_batch_out* out, const wbc_observer_state* obs, const void* tau_ext,
-                                          const void* plan, void* tau_traj, void* com_traj, void* stream) {
+static int rollout_tracking_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                                 const wbc_observer_state* obs, const void* tau_ext, const void* plan, void* tau_traj, void* com_traj,
+                                 void* stream, const void* payload) {
   if (!s || !in || !out || !plan) return fail(WBC_E_INVALID, "null argument");
   if (horizon < 1) return fail(WBC_E_INVALID, "horizon must be >= 1");
   if (!out->M || !out->h || !out->Jc) return fail(WBC_E_INVALID, "rollouts need the M, h, Jc buffers (forward dynamics reads them)");
@@ -1219,8 +1257,8 @@ extern "C" int wbc_rollout_tracking_batch(wbc_solver* s, size_t N, int horizon, 
       return fail(WBC_E_INVALID, "observer on: observer state buffers required");
     ON_DEVICE(s);
     hipStream_t st0 = (hipStream_t)stream;
-    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj)
-                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj);
+    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj, payload)
+                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj, payload);
   }
   wbc_batch_in tick = *in;
   tick.tau_prev = out->tau;
@@ -1243,11 +1281,26 @@ extern "C" int wbc_rollout_tracking_batch(wbc_solver* s, size_t N, int horizon, 
     void* traj = tau_traj ? (void*)((char*)tau_traj + (size_t)t * nj * N * ts) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     rc = s->dtype == WBC_F64
-             ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st)
-             : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st);
+             ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload)
+             : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload);
     if (rc) return rc;
   }
   return WBC_OK;
+}
+
+extern "C" int wbc_rollout_tracking_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in,
+                                          const wbc_batch_out* out, const wbc_observer_state* obs, const void* tau_ext,
+                                          const void* plan, void* tau_traj, void* com_traj, void* stream) {
+  return rollout_tracking_impl(s, N, horizon, in, out, obs, tau_ext, plan, tau_traj, com_traj, stream, nullptr);
+}
+
+extern "C" int wbc_rollout_tracking_plant_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                                                const wbc_observer_state* obs, const wbc_plant* plant, const void* plan, void* tau_traj,
+                                                void* com_traj, void* stream) {
+  const void *tau_ext, *payload;
+  const int rc = plant_args(plant, &tau_ext, &payload);
+  if (rc) return rc;
+  return rollout_tracking_impl(s, N, horizon, in, out, obs, tau_ext, plan, tau_traj, com_traj, stream, payload);
 }
 
 // ---- single-robot tick on the solver's pinned image.  Layout (scalars of the solver's dtype, then ints):
@@ -1466,4 +1519,4 @@ extern "C" const char* wbc_strerror(int st) {
   }
 }
 extern "C" const char* wbc_last_error(void) { return g_err.c_str(); }
-extern "C" int wbc_abi_version(void) { return 9; }  // 9: wbc_solver_options.fused_pair, wbc_tick_plan.fused = 3 (fused_pair_kernel); 8: wbc_solver_options.tile_tick, wbc_tick_plan.fused = 2 / qp_body = 2 (staged QP tiles); 7: wbc_solver_collect_timing_n (the unsized call writes 5 entries again), wbc_solver_options.multi_threads / multi_spin_us, wbc_multi_tick_gather / wbc_multi_issue_threads / wbc_multi_host_stats; 6: wbc_plan_tick / wbc_solver_plan_tick / wbc_dispatch_thresholds, wbc_solver_invalidate_structural, warm start (wbc_step_batch_warm, wbc_multi_step_batch_warm, wbc_solver_options.rollout_warm, wbc_tick_plan.qp_warm, WBC_PLAN_* flags), wbc_multi_allgather_tau_async / wbc_multi_gather_wait; 5: wbc_qp_dense_batch; 4: wbc_one_map / wbc_one_tick, wbc_solver_options.f32_pack2 and one_zerocopy 2 / 3 (options struct grows at its end: struct_size keeps version-3 callers valid); 3: wbc_solver_options / wbc_solver_create_ex, wbc_observer_init, wbc_multi_* (2: integrate takes Jc, timing arrays have 4 entries, reference / tracking entry points)
+extern "C" int wbc_abi_version(void) { return 10; }  // 10: wbc_plant, wbc_integrate_plant_batch / wbc_rollout_plant_batch / wbc_rollout_tracking_plant_batch (plant payload); 9: wbc_solver_options.fused_pair, wbc_tick_plan.fused = 3 (fused_pair_kernel); 8: wbc_solver_options.tile_tick, wbc_tick_plan.fused = 2 / qp_body = 2 (staged QP tiles); 7: wbc_solver_collect_timing_n (the unsized call writes 5 entries again), wbc_solver_options.multi_threads / multi_spin_us, wbc_multi_tick_gather / wbc_multi_issue_threads / wbc_multi_host_stats; 6: wbc_plan_tick / wbc_solver_plan_tick / wbc_dispatch_thresholds, wbc_solver_invalidate_structural, warm start (wbc_step_batch_warm, wbc_multi_step_batch_warm, wbc_solver_options.rollout_warm, wbc_tick_plan.qp_warm, WBC_PLAN_* flags), wbc_multi_allgather_tau_async / wbc_multi_gather_wait; 5: wbc_qp_dense_batch; 4: wbc_one_map / wbc_one_tick, wbc_solver_options.f32_pack2 and one_zerocopy 2 / 3 (options struct grows at its end: struct_size keeps version-3 callers valid); 3: wbc_solver_options / wbc_solver_create_ex, wbc_observer_init, wbc_multi_* (2: integrate takes Jc, timing arrays have 4 entries, reference / tracking entry points)
