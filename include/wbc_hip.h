@@ -339,6 +339,60 @@ int wbc_rollout_tracking_plant_batch(wbc_solver* s, size_t N, int horizon, const
                                      const wbc_observer_state* obs, const wbc_plant* plant, const void* plan, void* tau_traj,
                                      void* com_traj, void* stream);
 
+/* Scored rollouts: a running quadratic cost of a rollout's state path, accumulated on chip, and the choice of the best of K candidates per group --
+ * what a sampling MPC runs rollouts for (rollout -> cost -> argmin / MPPI weights, all on the stream, capturable in one hipGraph).
+ * ADDITIVE to ABI 10: wbc_abi_version() stays 10 and no existing struct changes; a caller detects the feature by these symbols (dlsym).
+ * Per state, for tick k = 0 .. H-1, on the state (q, v) the tick ENDS in (after its integrator step) and on the tau, f, status it produced:
+ *   l_k = w_tau sum_j tau_j^2 + w_f sum_i f_i^2 + w_fail [status_k != 0]
+ *       + s_k ( sum_c w_pos[c] (p_c - g_p[c])^2      p  = base position q[0..2]
+ *             + sum_c w_rot[c] e_c^2                 e  = the attitude error e_R of wbc_reference_batch with quat_des := g_quat, base quaternion q[3..6]
+ *             + sum_c w_vel[c] (v_c - g_v[c])^2      v  = base linear velocity v[0..2]
+ *             + sum_c w_omega[c] om_c^2              om = base angular velocity v[3..5]
+ *             + w_q sum_j (qj_j - q_nom_j)^2 + w_qd sum_j qdj_j^2 )      joints in the caller's order
+ *   s_k = 1 for k < H-1, s_(H-1) = terminal
+ *   cost = (accumulate ? cost_in : 0) + sum_k l_k        fail_ticks = (accumulate ? in : 0) + #{k : status_k != 0}
+ * goal [WBC_GOAL_WORDS][N], solver scalar type, component-major: g_p (3), g_quat (x, y, z, w), g_v (3).  Arithmetic and the sum in the solver's scalar type. */
+#define WBC_GOAL_WORDS 10
+typedef struct wbc_score_params {
+  size_t struct_size;    /* sizeof(wbc_score_params) of the caller's build */
+  double w_tau, w_f, w_fail;
+  double w_pos[3], w_rot[3], w_vel[3], w_omega[3];
+  double w_q, w_qd;
+  double terminal;       /* s_k of the last tick, >= 0 */
+  double q_nom[WBC_MAXV];
+} wbc_score_params;
+/* every weight 0 except w_fail = 1e6; terminal = 1; q_nom = 0 */
+void wbc_score_params_default(wbc_score_params* p);
+/* all weights and terminal >= 0 (WBC_E_INVALID otherwise).  The weights travel as a kernel argument: nothing is uploaded, later scored calls use them.
+ * Not inside a stream capture (a captured graph keeps the weights it was captured with). */
+int wbc_solver_set_score_params(wbc_solver* s, const wbc_score_params* p);
+typedef struct wbc_rollout_score {
+  size_t struct_size;    /* sizeof(wbc_rollout_score) of the caller's build */
+  const void* goal;      /* [WBC_GOAL_WORDS][N] */
+  void* cost;            /* [N], solver scalar type */
+  int* fail_ticks;       /* [N] int32 or NULL */
+  int accumulate;        /* 0: the sums start at zero; else at what cost / fail_ticks hold (a horizon continued over several calls) */
+} wbc_rollout_score;
+/* The superset rollout.  plant == NULL: the nominal plant; plan == NULL: constant references (com_traj must then be NULL).
+ * score == NULL or score->cost == NULL: exactly the existing entry point of that (plant, plan) combination -- same kernels, same bits.
+ * Scored launches of the one-launch path always start every tick after the first from the previous tick's active set (rollout_warm = 1:
+ * results do not depend on it).  Stream rules as for the other rollouts: no allocation, no synchronisation, hipGraph-capturable. */
+int wbc_rollout_scored_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                             const wbc_observer_state* obs, const wbc_plant* plant, const void* plan, void* tau_traj, void* com_traj,
+                             const wbc_rollout_score* score, void* stream);
+/* One tick's l_k, for callers that drive their own loop: q, v = the state the tick ended in, tau, f, status = what it produced;
+ * is_last selects s_k = terminal.  score->accumulate = 0: cost = l_k (the first tick of a sum); else l_k is added to score->cost. */
+int wbc_score_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* tau, const void* f, const int* status,
+                    const wbc_rollout_score* score, int is_last, void* stream);
+/* N = n_groups * group candidates; group g = states [g * group, (g + 1) * group), 1 <= group <= 4096.  Per group:
+ *   best [n_groups] int32 = index WITHIN the group of the smallest cost (ties: the lowest index; NaN counts as +inf; all +inf / NaN: -1)
+ *   best_cost [n_groups] (optional)
+ *   weights [N] (optional) = exp(-(c_i - c_min) / lambda) / their sum over the group (MPPI); lambda <= 0: one-hot on best;
+ *                            a group with best = -1 gets all-zero weights
+ * No solver: dtype (WBC_F64 / WBC_F32) names the scalar type; runs on the current device.  Bit-identical from run to run. */
+int wbc_rollout_select(int dtype, size_t n_groups, size_t group, const void* cost, double lambda, int* best, void* best_cost,
+                       void* weights, void* stream);
+
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
  * synchronises.  obs_integ/obs_r (host, nv each) are in/out and may be NULL when the observer is off. */

@@ -232,6 +232,15 @@ def lib():
         L.wbc_integrate_plant_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
         L.wbc_rollout_plant_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 6
         L.wbc_rollout_tracking_plant_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 8
+        # scored rollouts: additive to ABI 10, detected by the symbols (a library without them is an older build of the same ABI)
+        if not hasattr(L, "wbc_rollout_scored_batch"):
+            raise RuntimeError("%s lacks the scored-rollout entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+        L.wbc_score_params_default.argtypes = [C.c_void_p]
+        L.wbc_score_params_default.restype = None
+        L.wbc_solver_set_score_params.argtypes = [C.c_void_p, C.c_void_p]
+        L.wbc_rollout_scored_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 9
+        L.wbc_score_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+        L.wbc_rollout_select.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -264,6 +273,67 @@ PAYLOAD_WORDS = 10   # include/wbc_hip.h: WBC_PAYLOAD_WORDS
 class Plant(C.Structure):
     """wbc_plant (ABI 10): what the plant of wbc_*_plant_batch has that the controller's model lacks"""
     _fields_ = [("struct_size", C.c_size_t), ("tau_ext", C.c_void_p), ("payload", C.c_void_p)]
+
+
+GOAL_WORDS = 10   # include/wbc_hip.h: WBC_GOAL_WORDS -- goal [GOAL_WORDS, N]: g_p (3), g_quat (x, y, z, w), g_v (3)
+
+
+class ScoreParams(C.Structure):
+    """wbc_score_params: the weights of the running cost of the scored rollouts (include/wbc_hip.h)"""
+    _fields_ = [("struct_size", C.c_size_t), ("w_tau", C.c_double), ("w_f", C.c_double), ("w_fail", C.c_double),
+                ("w_pos", C.c_double * 3), ("w_rot", C.c_double * 3), ("w_vel", C.c_double * 3), ("w_omega", C.c_double * 3),
+                ("w_q", C.c_double), ("w_qd", C.c_double), ("terminal", C.c_double), ("q_nom", C.c_double * WBC_MAXV)]
+
+    @staticmethod
+    def default():
+        p = ScoreParams()
+        lib().wbc_score_params_default(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d):
+        """keys = field names; scalars for the 3-vectors broadcast; missing keys keep the defaults (all 0, w_fail = 1e6, terminal = 1)"""
+        p = ScoreParams.default()
+        for k, val in d.items():
+            if k in ("w_pos", "w_rot", "w_vel", "w_omega"):
+                a = np.broadcast_to(np.asarray(val, dtype=np.float64), (3,))
+                for i in range(3):
+                    getattr(p, k)[i] = float(a[i])
+            elif k == "q_nom":
+                for i, x in enumerate(np.asarray(val, dtype=np.float64).ravel()):
+                    p.q_nom[i] = float(x)
+            elif k in ("w_tau", "w_f", "w_fail", "w_q", "w_qd", "terminal"):
+                setattr(p, k, float(val))
+            else:
+                raise KeyError("ScoreParams has no field %r" % k)
+        return p
+
+
+class RolloutScore(C.Structure):
+    """wbc_rollout_score: the buffers of one scored call"""
+    _fields_ = [("struct_size", C.c_size_t), ("goal", C.c_void_p), ("cost", C.c_void_p), ("fail_ticks", C.c_void_p), ("accumulate", C.c_int)]
+
+
+def select_rollouts(cost, group, lam=0.0, want_weights=False, stream=None):
+    """Per group of `group` consecutive candidates of cost [N] (a contiguous CUDA tensor, float64 or float32; N = n_groups * group):
+    dict(best [n_groups] int32 = index within the group of the smallest cost (-1: none finite), best_cost [n_groups][, weights [N] = the MPPI
+    weights exp(-(c - c_min) / lam), normalised per group; lam <= 0: one-hot on best]).  wbc_rollout_select: one launch on the current stream."""
+    import torch
+    assert cost.is_cuda and cost.is_contiguous() and cost.dtype in (torch.float64, torch.float32)
+    N = cost.numel()
+    group = int(group)
+    if group < 1 or N % group:
+        raise ValueError("cost holds %d candidates: not a multiple of group = %d" % (N, group))
+    ng = N // group
+    out = dict(best=torch.empty(ng, dtype=torch.int32, device=cost.device), best_cost=torch.empty(ng, dtype=cost.dtype, device=cost.device))
+    if want_weights:
+        out["weights"] = torch.empty(N, dtype=cost.dtype, device=cost.device)
+    st = stream if stream is not None else torch.cuda.current_stream(cost.device).cuda_stream
+    with torch.cuda.device(cost.device):
+        _check(lib().wbc_rollout_select(F64 if cost.dtype == torch.float64 else F32, ng, group, C.c_void_p(cost.data_ptr()), C.c_double(lam),
+                                        C.c_void_p(out["best"].data_ptr()), C.c_void_p(out["best_cost"].data_ptr()),
+                                        C.c_void_p(out["weights"].data_ptr()) if want_weights else None, C.c_void_p(st)), "wbc_rollout_select")
+    return out
 
 
 def payload_rows(m, c, I):
@@ -535,6 +605,63 @@ class Solver:
         _check(lib().wbc_rollout_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob),
                                        self._ptr(tau_ext, m.nv, N), tt, self._stream()), "wbc_rollout_batch")
         return out
+
+    def set_score_params(self, p):
+        """p: ScoreParams or dict (see ScoreParams.from_dict): the weights of every later scored call of this solver."""
+        if isinstance(p, dict):
+            p = ScoreParams.from_dict(p)
+        _check(lib().wbc_solver_set_score_params(self._h, C.byref(p)), "wbc_solver_set_score_params")
+
+    def _score(self, goal, cost, fail_ticks, accumulate, N):
+        sc = RolloutScore()
+        sc.struct_size = C.sizeof(RolloutScore)
+        sc.goal = self._ptr(goal, GOAL_WORDS, N)
+        sc.cost = self._ptr(cost, 1, N)
+        sc.fail_ticks = self._ptr(fail_ticks, 1, N, self.torch.int32)
+        sc.accumulate = 1 if accumulate else 0
+        return sc
+
+    def rollout_scored(self, horizon, q, v, normals, mu, mask, out, w_des, vdot_des, goal, cost=None, fail_ticks=None, accumulate=False,
+                       plan=None, payload=None, obs_integ=None, obs_r=None, tau_ext=None, tau_traj=None, com_traj=None):
+        """rollout() (plan None: w_des / vdot_des are the constant references) or rollout_tracking() (plan given: they are scratch), with or without a
+        payload on the plant, AND the running cost of the state path against goal [GOAL_WORDS, N] under the solver's ScoreParams, accumulated on
+        chip (wbc_rollout_scored_batch).  cost [N] (allocated when None) and fail_ticks [N] int32 (optional) start at zero, or -- accumulate --
+        at what they hold.  Returns cost."""
+        torch = self.torch
+        m = self.model
+        N = q.shape[1]
+        if cost is None:
+            assert not accumulate, "accumulate needs the cost of the earlier call"
+            cost = torch.empty(N, dtype=self.tdtype, device=q.device)
+        rows = dict(tau=m.nj, f=3 * m.nf, M=m.nv * (m.nv + 1) // 2, h=m.nv, Jc=3 * m.nf * m.nv, pf=3 * m.nf)
+        bi = _BatchIn(self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(w_des, 6, N), self._ptr(vdot_des, m.nv, N),
+                      self._ptr(normals, 3 * m.nf, N), self._ptr(mu, m.nf, N), self._ptr(mask, 1, N, torch.int32), None, None)
+        g = lambda k: self._ptr(out.get(k), rows[k], N)
+        bo = _BatchOut(g("tau"), g("f"), self._ptr(out["status"], 1, N, torch.int32),
+                       self._ptr(out.get("iters"), 1, N, torch.int32), g("M"), g("h"), g("Jc"), g("pf"))
+        ob = _ObsState(self._ptr(obs_integ, m.nv, N), self._ptr(obs_r, m.nv, N))
+        tt = ct = None
+        if tau_traj is not None:
+            assert tau_traj.is_cuda and tau_traj.is_contiguous() and tau_traj.numel() == horizon * m.nj * N
+            tt = C.c_void_p(tau_traj.data_ptr())
+        if com_traj is not None:
+            assert com_traj.is_cuda and com_traj.is_contiguous() and com_traj.numel() == horizon * 6 * N
+            ct = C.c_void_p(com_traj.data_ptr())
+        pl = self._plant(tau_ext, payload, N) if (payload is not None or tau_ext is not None) else None
+        sc = self._score(goal, cost, fail_ticks, accumulate, N)
+        _check(lib().wbc_rollout_scored_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob), C.byref(pl) if pl is not None else None,
+                                              self._ptr(plan, PLAN_WORDS, N), tt, ct, C.byref(sc), self._stream()), "wbc_rollout_scored_batch")
+        return cost
+
+    def score(self, q, v, tau, f, status, goal, cost, fail_ticks=None, accumulate=True, is_last=False):
+        """One tick's cost l_k of the state (q, v) the tick ended in and the tau, f, status it produced, for callers that drive their own loop
+        (wbc_score_batch): added to cost [N] (accumulate, the default) or written to it (the first tick of a sum).  Returns cost."""
+        m = self.model
+        N = q.shape[1]
+        sc = self._score(goal, cost, fail_ticks, accumulate, N)
+        _check(lib().wbc_score_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(tau, m.nj, N), self._ptr(f, 3 * m.nf, N),
+                                     self._ptr(status, 1, N, self.torch.int32), C.byref(sc), 1 if is_last else 0, self._stream()), "wbc_score_batch")
+        return cost
 
     def set_ref_params(self, g):
         """g: RefParams or dict (see RefParams.from_dict)."""

@@ -125,6 +125,21 @@ template <class T> struct IntegrateArgs {
 #endif
 };
 
+// scored rollouts (score.hip.hpp): the weights of the running cost, and what a scoring launch reads and writes -- both kernel arguments BY VALUE, so a
+// scored call neither uploads nor allocates (hipGraph-capturable; wbc_solver_set_score_params only fills the solver's host copy)
+constexpr int GOAL_WORDS = 10;   // goal [GOAL_WORDS][N]: g_p (3), g_quat (x, y, z, w), g_v (3)
+template <class T> struct DevScoreW {
+  T w_tau, w_f, w_fail, w_pos[3], w_rot[3], w_vel[3], w_omega[3], w_q, w_qd, terminal;
+  T q_nom[12];   // caller's joint order
+};
+template <class T> struct ScoreArgs {
+  size_t N;
+  const T* goal; T* cost;
+  int* fail;        // [N] or null: ticks whose status != 0
+  int accumulate;   // 0: the sums start at zero, else at what cost / fail hold
+  DevScoreW<T> w;
+};
+
 // CoM reference generator (com_ref.hip.hpp)
 template <class T> struct DevRefParams {
   T kp_com[3], kd_com[3], kp_rot[3], kd_rot[3];

@@ -13,8 +13,20 @@
 #include <type_traits>
 #include "device_types.hpp"
 #include "dyn_sweep.hip.hpp"
+#include "score.hip.hpp"
 
 namespace wbc {
+
+// (SCORE, scored persistent rollout) what phase 2 needs to add this tick's cost: the call's ScoreArgs (a kernel argument) and the workgroup's LDS words --
+// the weights, goals [GOAL_WORDS][16], the running cost and failed ticks per lane of the integrator wavefront, this tick's status per state
+// where the sums go behind the last tick, parked in LDS by the kernel's prologue: held as kernel arguments they stay live through every role of every tick
+template <class T> struct ScoreOut { T* cost; int* fail; int accumulate; };
+template <class T> struct ScoreTick {
+  const ScoreOut<T>* out;
+  const DevScoreW<T>* w;   // the weights, in LDS
+  const T* goal; T* run; int* nfail; const int* stat;
+  bool first, last;   // tick 0 / the launch's last tick (wavefront-uniform)
+};
 
 // ---- plant payload (wbc_integrate_plant_batch, wbc_rollout_plant_batch, wbc_rollout_tracking_plant_batch)
 // A rigid body fixed to the trunk: p = [m, c (3, base frame), I about c (6, base axes: xx yy zz xy xz yz)], [PAYLOAD_WORDS][N] in memory.
@@ -95,10 +107,12 @@ constexpr int INT_FACT_WORDS = 27;
 // PAYLOAD (plant model mismatch, `payload` = [PAYLOAD_WORDS][N]): phase 1 adds dM_bb to the base block (with HAND: one more body in the composite
 // (m, R h, R I R^T) before the block is rebuilt), phase 2 subtracts dh_b from the base right-hand side.  false: the code of rounds 1-6, unchanged.
 template <class T, int SPW = 16, class Between = IntegrateNoWait, int PHASE = 0, bool UNGUARD = false, bool HAND = false, bool RESI = false,
-          class AfterState = IntegrateNoWait, bool SIMG_ = false, bool PAYLOAD = false>
+          class AfterState = IntegrateNoWait, bool SIMG_ = false, bool PAYLOAD = false, bool SCORE = false>
 WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const IntegrateArgs<T>& a, Between between = Between(), const T* hand_ = nullptr,
-                            const T* res_ = nullptr, T* fact = nullptr, AfterState after_state = AfterState(), const T* payload = nullptr) {
+                            const T* res_ = nullptr, T* fact = nullptr, AfterState after_state = AfterState(), const T* payload = nullptr,
+                            const ScoreTick<T>* sc = nullptr) {
   static_assert(PHASE == 0 || PHASE == 1 || PHASE == 2, "phase");
+  static_assert(!SCORE || (PHASE == 2 && RESI && SIMG_), "the cost is accumulated in phase 2 of the persistent rollout");
   static_assert(PHASE == 0 || HAND, "the split phases hand M's blocks over in LDS");
   constexpr bool FASTR = PHASE != 0 && SIMG_;   // (rollout workgroups with the state image) rsqrt_fast, see dyn_sweep.hip.hpp
   const T* const hand = HAND ? hand_ : nullptr;
@@ -476,6 +490,44 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
     if (leg < 3) STV(a.q, 4 + leg, sel4<T>(leg, qn[4], qn[5], qn[6], qn[6]));
   }
   ISTAMP(11);   // base rows stored
+  // SCORE: this tick's cost, on the state the tick ends in -- behind the state's stores, where nothing of the integrator is live any more.  A state is spread
+  // over its four leg rows: each row adds its own three joints' tau, qj, qdj and its foot's f, READ BACK from the result image (the QP wavefronts' words,
+  // acquired above) and from the state image (this lane's own words of a moment ago: one wavefront's LDS traffic is in program order) so that they occupy no
+  // register through the solves; row 0 also adds the base terms and the status.  The running sum is an LDS word per lane; the rows are summed behind the
+  // LAST tick.  (lanes beyond the workgroup's states duplicate a live state in lockstep -- UNGUARD -- and only the live row-0 lane stores)
+  if constexpr (SCORE) {
+    // (the weights never change after the prologue: read at a fixed LDS address they are loop-invariant, and the compiler lifts all ~30 reads out of the
+    //  horizon loop, where they sit in registers -- and in scratch -- through every role of every tick.  A zero it cannot see through keeps them here:
+    //  tx went through an empty asm above and is below 2^31)
+    const int z = (int)(tx >> 31);
+    const DevScoreW<T>& wt = *(sc->w + z);
+    const int slot = (int)(s32 - (unsigned)((size_t)blockIdx.x * SPW));
+    const int ln = (int)(tx & 63);
+    T g[GOAL_WORDS];
+#pragma unroll
+    for (int c = 0; c < GOAL_WORDS; ++c) g[c] = sc->goal[c * 16 + slot];
+    const int st = sc->stat[slot];
+    T t3[3], f3[3], q3[3], qd3[3], qn3[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      t3[k] = rs[jx[k] * 16]; f3[k] = rs[(12 + 3 * leg + k) * 16];
+      q3[k] = si_[(7 + jx[k]) * 16]; qd3[k] = si_[(SIMG_V + 6 + jx[k]) * 16]; qn3[k] = wt.q_nom[jx[k]];
+    }
+    const T lk = score_stage<T>(wt, sc->last ? wt.terminal : (T)1, t3, f3, q3, qd3, qn3, leg == 0, qn, vbn, g, st);
+    const T run = (sc->first ? (T)0 : sc->run[ln]) + lk;
+    const int nf = (sc->first ? 0 : sc->nfail[ln]) + (st != 0 ? 1 : 0);
+    if (!sc->last) { sc->run[ln] = run; sc->nfail[ln] = nf; }
+    else {
+      const T total = xrow_sum(run);
+      if (live && leg == 0) {
+        const bool acc = sc->out->accumulate != 0;
+        T* const cp = (T*)((char*)sc->out->cost + (size_t)(s32 * (unsigned)sizeof(T)));
+        *cp = acc ? *cp + total : total;
+        int* const fl0 = sc->out->fail;
+        if (fl0) { int* const fp = fl0 + s32; *fp = (acc ? *fp : 0) + nf; }
+      }
+    }
+  }
 #undef ISTAMP
 #undef STS
 #undef STV

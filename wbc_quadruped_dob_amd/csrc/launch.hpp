@@ -86,6 +86,14 @@ template <class T> hipError_t k_fused_pair(const LaunchCtx& L, const DevModel<T>
 template <class T> hipError_t k_rollout(const LaunchCtx& L, bool observer, bool track, int spw, const DevModel<T>* model, const DevParams<T>& prm,
                                        const SweepArgs<T>& a, const QpArgs<T>& qa, const QpJidx& jmap, const IntegrateArgs<T>& ia, int horizon,
                                        const DevRefParams<T>* G, const RefArgs<T>& ra, bool warm = false, const T* payload = nullptr);
+// rollout_scored_kernel<T, OBSERVER, TRACK, SPW, PAYLOAD>: k_rollout with the running cost accumulated on chip (score.hip.hpp; units k_rollout_sc*); always warm
+template <class T> hipError_t k_rollout_scored(const LaunchCtx& L, bool observer, bool track, int spw, const DevModel<T>* model, const DevParams<T>& prm,
+                                              const SweepArgs<T>& a, const QpArgs<T>& qa, const QpJidx& jmap, const IntegrateArgs<T>& ia, int horizon,
+                                              const DevRefParams<T>* G, const RefArgs<T>& ra, const T* payload, const ScoreArgs<T>& sc);
+// score_tick_kernel<T>: one tick's cost l_k of every state into sc.cost / sc.fail (the per-tick path of the scored rollouts, wbc_score_batch)
+template <class T> hipError_t k_score_tick(const LaunchCtx& L, const ScoreArgs<T>& sc, const T* q, const T* v, const T* tau, const T* f, const int* status, int is_last);
+// rollout_select_kernel<T, BLOCK>: per group of `group` consecutive costs the best index, its cost and the MPPI weights (one workgroup per group)
+template <class T> hipError_t k_rollout_select(hipStream_t st, size_t n_groups, size_t group, const T* cost, T lambda, int* best, T* best_cost, T* weights);
 // qp_general_kernel<T>: dense QPs of run-time size (n <= 36 variables, m <= 64 rows, the first meq of them equalities), one per wavefront
 template <class T> hipError_t k_qp_general(const LaunchCtx& L, const QpGeneralArgs<T>& a);
 // one thread: *ptr = value, system scope (the completion ticket of the flag-polled single-robot tick)

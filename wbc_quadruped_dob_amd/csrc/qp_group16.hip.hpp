@@ -161,6 +161,8 @@ struct QpSync {
   // blocks from its words 24 .. 32 (row m of foot f, joint k at (24 + 3 m + k) * 64 + 16 f + slot) once `hand_flag` has reached `need_hand`, and the rnea
   // role does not compute them (RS_NOJC)
   const void* hand = nullptr; int* hand_flag = nullptr; int need_hand = 0;
+  // (scored persistent rollout, score.hip.hpp) an LDS word per state of the workgroup that receives this tick's status beside the result image
+  int* stat = nullptr;
 };
 #ifdef WBC_FUSED_STAMP
 // (one column per workgroup: column = first state of the workgroup, i.e. blockIdx.x * states-per-workgroup)

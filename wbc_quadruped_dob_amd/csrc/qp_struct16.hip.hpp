@@ -806,6 +806,7 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
         }
       }
     }
+    if constexpr (WSLDS) { if (sync && sync->stat && l16 == 0) sync->stat[(int)(tx >> 4)] = status; }
     if constexpr (STG != 0) {
       if (l16 == 0) { who.iimg[who.tile + stg_slot] = status; who.iimg[2 * who.tile + stg_slot] = iter; }
     } else if (l16 == 0 && to_mem) {

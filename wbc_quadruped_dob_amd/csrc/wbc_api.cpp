@@ -89,6 +89,7 @@ struct wbc_solver {
   hipStream_t aux = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   void* d_ref = nullptr;     // DevRefParams<T>, set by wbc_solver_set_ref_params
+  wbc_score_params score;    // the weights of the scored rollouts (wbc_solver_set_score_params; kernel arguments by value), defaults at creation
   // N=1 convenience buffers
   void* d_one = nullptr;
   void* h_one = nullptr;       // pinned host image of d_one: the single-robot calls move it with ONE copy each way
@@ -650,6 +651,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   wbc_solver* s = new (std::nothrow) wbc_solver;
   if (!s) return fail(WBC_E_INVALID, "out of memory");
   s->dtype = dtype; s->device = device; s->max_batch = max_batch; s->params = *p; s->opt = o;
+  wbc_score_params_default(&s->score);
   s->rz = resolve_options(dtype, o);
   std::memcpy(s->leg_body, leg_body, sizeof(leg_body));
   for (int l = 0; l < 4; ++l) for (int k = 0; k < 3; ++k) s->jmap.j[3 * l + k] = leg_body[l][k] - 1;
@@ -1079,11 +1081,46 @@ extern "C" int wbc_integrate_plant_batch(wbc_solver* s, size_t N, void* q, void*
                              : integrate_impl<float>(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, st, payload);
 }
 
+// ---- scored rollouts (score.hip.hpp): the solver's weights and the call's buffers as ONE kernel argument
+template <class T> static ScoreArgs<T> score_args(const wbc_solver* s, size_t N, const wbc_rollout_score* score, bool accumulate) {
+  ScoreArgs<T> a;
+  std::memset(&a, 0, sizeof(a));
+  const wbc_score_params& p = s->score;
+  a.N = N; a.goal = (const T*)score->goal; a.cost = (T*)score->cost; a.fail = score->fail_ticks; a.accumulate = accumulate ? 1 : 0;
+  a.w.w_tau = (T)p.w_tau; a.w.w_f = (T)p.w_f; a.w.w_fail = (T)p.w_fail; a.w.w_q = (T)p.w_q; a.w.w_qd = (T)p.w_qd; a.w.terminal = (T)p.terminal;
+  for (int i = 0; i < 3; ++i) { a.w.w_pos[i] = (T)p.w_pos[i]; a.w.w_rot[i] = (T)p.w_rot[i]; a.w.w_vel[i] = (T)p.w_vel[i]; a.w.w_omega[i] = (T)p.w_omega[i]; }
+  for (int i = 0; i < 12; ++i) a.w.q_nom[i] = (T)p.q_nom[i];
+  return a;
+}
+// score == NULL or score->cost == NULL: the unscored call (*use = NULL); otherwise struct_size first (as wbc_plant), then goal and cost together
+static int score_arg_check(const wbc_rollout_score* score, const wbc_rollout_score** use) {
+  *use = nullptr;
+  if (!score) return WBC_OK;
+  if (score->struct_size < sizeof(wbc_rollout_score)) return fail(WBC_E_INVALID, "wbc_rollout_score: struct_size too small");
+  if (!score->cost) {
+    if (score->goal || score->fail_ticks) return fail(WBC_E_INVALID, "wbc_rollout_score: goal / fail_ticks without cost");
+    return WBC_OK;
+  }
+  if (!score->goal) return fail(WBC_E_INVALID, "wbc_rollout_score: cost without goal");
+  *use = score;
+  return WBC_OK;
+}
+// the per-tick path: one tick's l_k behind the tick's integrate launch (score_tick_kernel)
+static int score_tick(wbc_solver* s, size_t N, const void* q, const void* v, const void* tau, const void* f, const int* status,
+                      const wbc_rollout_score* score, bool accumulate, int is_last, hipStream_t st) {
+  LaunchCtx L; L.st = st;
+  hipError_t e;
+  if (s->dtype == WBC_F64) e = k_score_tick<double>(L, score_args<double>(s, N, score, accumulate), (const double*)q, (const double*)v, (const double*)tau, (const double*)f, status, is_last);
+  else e = k_score_tick<float>(L, score_args<float>(s, N, score, accumulate), (const float*)q, (const float*)v, (const float*)tau, (const float*)f, status, is_last);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("score launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
 // small batches: the whole horizon in ONE launch (rollout_kernel, fused_tick.hip.hpp)
 template <class T>
 static int rollout_persistent(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
                               const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, hipStream_t st,
-                              const void* plan = nullptr, void* com_traj = nullptr, const void* payload = nullptr) {
+                              const void* plan = nullptr, void* com_traj = nullptr, const void* payload = nullptr, const wbc_rollout_score* score = nullptr) {
   SweepArgs<T> a;
   std::memset(&a, 0, sizeof(a));
   a.jpack = s->jpack;
@@ -1117,6 +1154,12 @@ static int rollout_persistent(wbc_solver* s, size_t N, int horizon, const wbc_ba
   ra.N = N; ra.q = (const T*)in->q; ra.v = (const T*)in->v; ra.plan = (const T*)plan; ra.t = (T)0;
   ra.w_des = (T*)in->w_des; ra.vdot_des = (T*)in->vdot_des; ra.com = (T*)com_traj;
   timing_tick(s);
+  if (score) {   // the scored sibling of the same kernel (always warm)
+    const ScoreArgs<T> sc = score_args<T>(s, N, score, score->accumulate != 0);
+    TIMED_LAUNCH(5, st, "scored rollout", k_rollout_scored<T>(L, s->params.observer_order > 0, plan != nullptr, spw, dev_model<T>(s), to_dev_params<T>(s->params), a, qa,
+                                                              s->jmap, ia, horizon, (const DevRefParams<T>*)s->d_ref, ra, (const T*)payload, sc));
+    return WBC_OK;
+  }
   TIMED_LAUNCH(5, st, "rollout", k_rollout<T>(L, s->params.observer_order > 0, plan != nullptr, spw, dev_model<T>(s), to_dev_params<T>(s->params), a, qa,
                                               s->jmap, ia, horizon, (const DevRefParams<T>*)s->d_ref, ra, s->opt.rollout_warm != 0, (const T*)payload));
   return WBC_OK;
@@ -1126,9 +1169,11 @@ static bool rollout_as_one_launch(const wbc_solver* s, size_t N) { return N <= s
 
 // wbc_rollout_batch; payload (wbc_rollout_plant_batch): the plant's trunk carries it, in the persistent kernel and in the per-tick integrate launches alike
 static int rollout_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
-                        const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, void* stream, const void* payload) {
+                        const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, void* stream, const void* payload,
+                        const wbc_rollout_score* score = nullptr) {
   if (!s || !in || !out) return fail(WBC_E_INVALID, "null argument");
   if (horizon < 1) return fail(WBC_E_INVALID, "horizon must be >= 1");
+  if (score && !out->status) return fail(WBC_E_INVALID, "scored rollouts need the status buffer");
   if (!out->M || !out->h || !out->Jc) return fail(WBC_E_INVALID, "rollouts need the M, h, Jc buffers (forward dynamics reads them)");
   if (N == 0) return WBC_OK;   // empty shard
   if (rollout_as_one_launch(s, N)) {
@@ -1140,8 +1185,8 @@ static int rollout_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in
       return fail(WBC_E_INVALID, "observer on: observer state buffers required");
     ON_DEVICE(s);
     hipStream_t st0 = (hipStream_t)stream;
-    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, nullptr, nullptr, payload)
-                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, nullptr, nullptr, payload);
+    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, nullptr, nullptr, payload, score)
+                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, nullptr, nullptr, payload, score);
   }
   wbc_batch_in tick = *in;
   tick.tau_prev = out->tau;  // the previous tick's outputs are this tick's tau_prev / f_prev: the sweep reads them
@@ -1166,6 +1211,10 @@ static int rollout_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in
              ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload)
              : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload);
     if (rc) return rc;
+    if (score) {
+      rc = score_tick(s, N, in->q, in->v, out->tau, out->f, out->status, score, t > 0 || score->accumulate != 0, t == horizon - 1, st);
+      if (rc) return rc;
+    }
   }
   return WBC_OK;
 }
@@ -1242,9 +1291,10 @@ extern "C" int wbc_reference_batch(wbc_solver* s, size_t N, const void* q, const
 
 static int rollout_tracking_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
                                  const wbc_observer_state* obs, const void* tau_ext, const void* plan, void* tau_traj, void* com_traj,
-                                 void* stream, const void* payload) {
+                                 void* stream, const void* payload, const wbc_rollout_score* score = nullptr) {
   if (!s || !in || !out || !plan) return fail(WBC_E_INVALID, "null argument");
   if (horizon < 1) return fail(WBC_E_INVALID, "horizon must be >= 1");
+  if (score && !out->status) return fail(WBC_E_INVALID, "scored rollouts need the status buffer");
   if (!out->M || !out->h || !out->Jc) return fail(WBC_E_INVALID, "rollouts need the M, h, Jc buffers (forward dynamics reads them)");
   if (!in->q || !in->v || !in->w_des || !in->vdot_des) return fail(WBC_E_INVALID, "null input buffer");
   if (!s->d_ref) return fail(WBC_E_INVALID, "call wbc_solver_set_ref_params first");
@@ -1257,8 +1307,8 @@ static int rollout_tracking_impl(wbc_solver* s, size_t N, int horizon, const wbc
       return fail(WBC_E_INVALID, "observer on: observer state buffers required");
     ON_DEVICE(s);
     hipStream_t st0 = (hipStream_t)stream;
-    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj, payload)
-                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj, payload);
+    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj, payload, score)
+                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj, payload, score);
   }
   wbc_batch_in tick = *in;
   tick.tau_prev = out->tau;
@@ -1284,6 +1334,10 @@ static int rollout_tracking_impl(wbc_solver* s, size_t N, int horizon, const wbc
              ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload)
              : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload);
     if (rc) return rc;
+    if (score) {
+      rc = score_tick(s, N, in->q, in->v, out->tau, out->f, out->status, score, t > 0 || score->accumulate != 0, t == horizon - 1, st);
+      if (rc) return rc;
+    }
   }
   return WBC_OK;
 }
@@ -1301,6 +1355,69 @@ extern "C" int wbc_rollout_tracking_plant_batch(wbc_solver* s, size_t N, int hor
   const int rc = plant_args(plant, &tau_ext, &payload);
   if (rc) return rc;
   return rollout_tracking_impl(s, N, horizon, in, out, obs, tau_ext, plan, tau_traj, com_traj, stream, payload);
+}
+
+// ---- scored rollouts: the weights, the superset rollout, one tick's cost, the per-group selection
+extern "C" void wbc_score_params_default(wbc_score_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->w_fail = 1e6;
+  p->terminal = 1;
+}
+
+extern "C" int wbc_solver_set_score_params(wbc_solver* s, const wbc_score_params* p) {
+  if (!p) return fail(WBC_E_INVALID, "null argument");
+  if (p->struct_size < sizeof(wbc_score_params)) return fail(WBC_E_INVALID, "wbc_score_params: struct_size too small (call wbc_score_params_default first)");
+  const double w[] = {p->w_tau, p->w_f, p->w_fail, p->w_pos[0], p->w_pos[1], p->w_pos[2], p->w_rot[0], p->w_rot[1], p->w_rot[2], p->w_vel[0], p->w_vel[1], p->w_vel[2],
+                      p->w_omega[0], p->w_omega[1], p->w_omega[2], p->w_q, p->w_qd, p->terminal};
+  for (double x : w)
+    if (!(x >= 0)) return fail(WBC_E_INVALID, "wbc_score_params: weights and terminal must be non-negative");
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  s->score = *p;
+  return WBC_OK;
+}
+
+extern "C" int wbc_rollout_scored_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                                        const wbc_observer_state* obs, const wbc_plant* plant, const void* plan, void* tau_traj, void* com_traj,
+                                        const wbc_rollout_score* score, void* stream) {
+  const wbc_rollout_score* use;
+  int rc = score_arg_check(score, &use);
+  if (rc) return rc;
+  const void *tau_ext, *payload;
+  rc = plant_args(plant, &tau_ext, &payload);
+  if (rc) return rc;
+  if (!plan) {
+    if (com_traj) return fail(WBC_E_INVALID, "com_traj needs a plan (the planner records it)");
+    return rollout_impl(s, N, horizon, in, out, obs, tau_ext, tau_traj, stream, payload, use);
+  }
+  return rollout_tracking_impl(s, N, horizon, in, out, obs, tau_ext, plan, tau_traj, com_traj, stream, payload, use);
+}
+
+extern "C" int wbc_score_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* tau, const void* f, const int* status,
+                               const wbc_rollout_score* score, int is_last, void* stream) {
+  if (!s || !score) return fail(WBC_E_INVALID, "null argument");
+  if (score->struct_size < sizeof(wbc_rollout_score)) return fail(WBC_E_INVALID, "wbc_rollout_score: struct_size too small");
+  if (!score->goal || !score->cost) return fail(WBC_E_INVALID, "wbc_rollout_score: goal and cost are required");
+  if (!q || !v || !tau || !f || !status) return fail(WBC_E_INVALID, "null argument");
+  if (N == 0) return WBC_OK;
+  ON_DEVICE(s);
+  return score_tick(s, N, q, v, tau, f, status, score, score->accumulate != 0, is_last != 0, (hipStream_t)stream);
+}
+
+extern "C" int wbc_rollout_select(int dtype, size_t n_groups, size_t group, const void* cost, double lambda, int* best, void* best_cost,
+                                  void* weights, void* stream) {
+  if (dtype != WBC_F64 && dtype != WBC_F32) return fail(WBC_E_INVALID, "dtype must be WBC_F64 or WBC_F32");
+  if (group < 1 || group > 4096) return fail(WBC_E_INVALID, "group must be in 1 .. 4096");
+  if (n_groups > (size_t)0x7fffffff) return fail(WBC_E_INVALID, "n_groups is out of range (one workgroup per group)");   // (so n_groups * group cannot overflow)
+  if (!cost || !best) return fail(WBC_E_INVALID, "null argument");
+  if (n_groups == 0) return WBC_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = dtype == WBC_F64
+      ? k_rollout_select<double>(st, n_groups, group, (const double*)cost, lambda, best, (double*)best_cost, (double*)weights)
+      : k_rollout_select<float>(st, n_groups, group, (const float*)cost, (float)lambda, best, (float*)best_cost, (float*)weights);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("select launch: ") + hipGetErrorString(e));
+  return WBC_OK;
 }
 
 // ---- single-robot tick on the solver's pinned image.  Layout (scalars of the solver's dtype, then ints):
