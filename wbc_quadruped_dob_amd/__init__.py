@@ -449,6 +449,27 @@ class Solver:
         assert t.numel() == rows * N, (tuple(t.shape), rows, N)
         return C.c_void_p(t.data_ptr())
 
+    def _batch(self, N, q, v, w_des, vdot_des, normals, mu, mask, out, obs_integ, obs_r, tau_prev=None, f_prev=None):
+        """The C argument structs of a tick or a rollout: (_BatchIn, _BatchOut, _ObsState)."""
+        torch = self.torch
+        m = self.model
+        rows = dict(tau=m.nj, f=3 * m.nf, M=m.nv * (m.nv + 1) // 2, h=m.nv, Jc=3 * m.nf * m.nv, pf=3 * m.nf)
+        bi = _BatchIn(self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(w_des, 6, N), self._ptr(vdot_des, m.nv, N),
+                      self._ptr(normals, 3 * m.nf, N), self._ptr(mu, m.nf, N), self._ptr(mask, 1, N, torch.int32),
+                      self._ptr(tau_prev, m.nj, N), self._ptr(f_prev, 3 * m.nf, N))
+        g = lambda k: self._ptr(out.get(k), rows[k], N)
+        bo = _BatchOut(g("tau"), g("f"), self._ptr(out["status"], 1, N, torch.int32),
+                       self._ptr(out.get("iters"), 1, N, torch.int32), g("M"), g("h"), g("Jc"), g("pf"))
+        return bi, bo, _ObsState(self._ptr(obs_integ, m.nv, N), self._ptr(obs_r, m.nv, N))
+
+    @staticmethod
+    def _traj(t, words):
+        """A rollout's trajectory buffer (tau_traj, com_traj: horizon * rows * N words, or None) as the C call takes it."""
+        if t is None:
+            return None
+        assert t.is_cuda and t.is_contiguous() and t.numel() == words
+        return C.c_void_p(t.data_ptr())
+
     def empty(self, rows, N, dtype=None):
         return self.torch.empty((rows, N), dtype=dtype or self.tdtype, device=self.device)
 
@@ -490,13 +511,7 @@ class Solver:
             for k in ("M", "h", "Jc", "pf"):
                 if k not in out:
                     out[k] = self.empty(rows[k], N)
-        bi = _BatchIn(self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(w_des, 6, N), self._ptr(vdot_des, m.nv, N),
-                      self._ptr(normals, 3 * m.nf, N), self._ptr(mu, m.nf, N), self._ptr(mask, 1, N, torch.int32),
-                      self._ptr(tau_prev, m.nj, N), self._ptr(f_prev, 3 * m.nf, N))
-        g = lambda k: self._ptr(out.get(k), rows[k], N)
-        bo = _BatchOut(g("tau"), g("f"), self._ptr(out["status"], 1, N, torch.int32),
-                       self._ptr(out["iters"], 1, N, torch.int32), g("M"), g("h"), g("Jc"), g("pf"))
-        ob = _ObsState(self._ptr(obs_integ, m.nv, N), self._ptr(obs_r, m.nv, N))
+        bi, bo, ob = self._batch(N, q, v, w_des, vdot_des, normals, mu, mask, out, obs_integ, obs_r, tau_prev, f_prev)
         warm = warm or active_in is not None
         if warm and "active" not in out:
             out["active"] = torch.zeros(N, dtype=torch.int32, device=self.device)
@@ -583,20 +598,10 @@ class Solver:
         iters, M, h, Jc (e.g. the dict a previous step(..., want_mats=True) returned).
         payload [PAYLOAD_WORDS, N] (optional, see payload_rows): the PLANT carries it on its trunk, the controller keeps the nominal model
         (wbc_rollout_plant_batch)."""
-        torch = self.torch
         m = self.model
         N = q.shape[1]
-        rows = dict(tau=m.nj, f=3 * m.nf, M=m.nv * (m.nv + 1) // 2, h=m.nv, Jc=3 * m.nf * m.nv, pf=3 * m.nf)
-        bi = _BatchIn(self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(w_des, 6, N), self._ptr(vdot_des, m.nv, N),
-                      self._ptr(normals, 3 * m.nf, N), self._ptr(mu, m.nf, N), self._ptr(mask, 1, N, torch.int32), None, None)
-        g = lambda k: self._ptr(out.get(k), rows[k], N)
-        bo = _BatchOut(g("tau"), g("f"), self._ptr(out["status"], 1, N, torch.int32),
-                       self._ptr(out.get("iters"), 1, N, torch.int32), g("M"), g("h"), g("Jc"), g("pf"))
-        ob = _ObsState(self._ptr(obs_integ, m.nv, N), self._ptr(obs_r, m.nv, N))
-        tt = None
-        if tau_traj is not None:
-            assert tau_traj.is_cuda and tau_traj.is_contiguous() and tau_traj.numel() == horizon * m.nj * N
-            tt = C.c_void_p(tau_traj.data_ptr())
+        bi, bo, ob = self._batch(N, q, v, w_des, vdot_des, normals, mu, mask, out, obs_integ, obs_r)
+        tt = self._traj(tau_traj, horizon * m.nj * N)
         if payload is not None:
             pl = self._plant(tau_ext, payload, N)
             _check(lib().wbc_rollout_plant_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob), C.byref(pl), tt,
@@ -633,20 +638,8 @@ class Solver:
         if cost is None:
             assert not accumulate, "accumulate needs the cost of the earlier call"
             cost = torch.empty(N, dtype=self.tdtype, device=q.device)
-        rows = dict(tau=m.nj, f=3 * m.nf, M=m.nv * (m.nv + 1) // 2, h=m.nv, Jc=3 * m.nf * m.nv, pf=3 * m.nf)
-        bi = _BatchIn(self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(w_des, 6, N), self._ptr(vdot_des, m.nv, N),
-                      self._ptr(normals, 3 * m.nf, N), self._ptr(mu, m.nf, N), self._ptr(mask, 1, N, torch.int32), None, None)
-        g = lambda k: self._ptr(out.get(k), rows[k], N)
-        bo = _BatchOut(g("tau"), g("f"), self._ptr(out["status"], 1, N, torch.int32),
-                       self._ptr(out.get("iters"), 1, N, torch.int32), g("M"), g("h"), g("Jc"), g("pf"))
-        ob = _ObsState(self._ptr(obs_integ, m.nv, N), self._ptr(obs_r, m.nv, N))
-        tt = ct = None
-        if tau_traj is not None:
-            assert tau_traj.is_cuda and tau_traj.is_contiguous() and tau_traj.numel() == horizon * m.nj * N
-            tt = C.c_void_p(tau_traj.data_ptr())
-        if com_traj is not None:
-            assert com_traj.is_cuda and com_traj.is_contiguous() and com_traj.numel() == horizon * 6 * N
-            ct = C.c_void_p(com_traj.data_ptr())
+        bi, bo, ob = self._batch(N, q, v, w_des, vdot_des, normals, mu, mask, out, obs_integ, obs_r)
+        tt, ct = self._traj(tau_traj, horizon * m.nj * N), self._traj(com_traj, horizon * 6 * N)
         pl = self._plant(tau_ext, payload, N) if (payload is not None or tau_ext is not None) else None
         sc = self._score(goal, cost, fail_ticks, accumulate, N)
         _check(lib().wbc_rollout_scored_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob), C.byref(pl) if pl is not None else None,
@@ -689,23 +682,10 @@ class Solver:
                          tau_ext=None, tau_traj=None, com_traj=None, payload=None):
         """rollout() with the planner in the loop: w_des / vdot_des are scratch buffers regenerated every tick.
         payload: as in rollout() (wbc_rollout_tracking_plant_batch)."""
-        torch = self.torch
         m = self.model
         N = q.shape[1]
-        rows = dict(tau=m.nj, f=3 * m.nf, M=m.nv * (m.nv + 1) // 2, h=m.nv, Jc=3 * m.nf * m.nv, pf=3 * m.nf)
-        bi = _BatchIn(self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(w_des, 6, N), self._ptr(vdot_des, m.nv, N),
-                      self._ptr(normals, 3 * m.nf, N), self._ptr(mu, m.nf, N), self._ptr(mask, 1, N, torch.int32), None, None)
-        g = lambda k: self._ptr(out.get(k), rows[k], N)
-        bo = _BatchOut(g("tau"), g("f"), self._ptr(out["status"], 1, N, torch.int32),
-                       self._ptr(out.get("iters"), 1, N, torch.int32), g("M"), g("h"), g("Jc"), g("pf"))
-        ob = _ObsState(self._ptr(obs_integ, m.nv, N), self._ptr(obs_r, m.nv, N))
-        tt = ct = None
-        if tau_traj is not None:
-            assert tau_traj.is_cuda and tau_traj.is_contiguous() and tau_traj.numel() == horizon * m.nj * N
-            tt = C.c_void_p(tau_traj.data_ptr())
-        if com_traj is not None:
-            assert com_traj.is_cuda and com_traj.is_contiguous() and com_traj.numel() == horizon * 6 * N
-            ct = C.c_void_p(com_traj.data_ptr())
+        bi, bo, ob = self._batch(N, q, v, w_des, vdot_des, normals, mu, mask, out, obs_integ, obs_r)
+        tt, ct = self._traj(tau_traj, horizon * m.nj * N), self._traj(com_traj, horizon * 6 * N)
         if payload is not None:
             pl = self._plant(tau_ext, payload, N)
             _check(lib().wbc_rollout_tracking_plant_batch(self._h, N, int(horizon), C.byref(bi), C.byref(bo), C.byref(ob), C.byref(pl),

@@ -1,6 +1,6 @@
 // Host-callable launchers of the gfx950 kernels.  Each kernel family is its own translation unit (k_*.hip), compiled
 // once per scalar type (-DWBC_SCALAR=double|float), so the library builds in parallel and a change to one kernel
-// recompiles only the units that contain it.  The host side (wbc_api.hip, wbc_multi.cpp) sees nothing but these
+// recompiles only the units that contain it.  The host side (wbc_api.cpp, wbc_multi.cpp) sees nothing but these
 // declarations and the plain-data argument structs of device_types.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -81,15 +81,21 @@ template <class T> hipError_t k_fused_tick(const LaunchCtx& L, bool observer, bo
 //  4 352: 20.0 / 18.5, 5 000: 21.3 / 19.6, 6 000: 24.4 / 20.5, 7 500: 24.4 / 20.3, 8 191: 27.4 / 21.1 -- profiles/r06y3_ab_fused_pair_ragged.log)
 constexpr long long WBC_FUSED_PAIR_MIN = 4225, WBC_FUSED_PAIR_MAX = 8192, WBC_FUSED_PAIR_MAX_F32 = 16384;
 template <class T> hipError_t k_fused_pair(const LaunchCtx& L, const DevModel<T>* model, const DevParams<T>& prm, const SweepArgs<T>& a, const QpArgs<T>& qa, const QpJidx& jmap);
-// rollout_kernel<T, OBSERVER, TRACK, SPW, WARM, PAYLOAD>: `horizon` dependent ticks incl. forward dynamics (and the planner) as one launch;
-// payload (non-null, [10][N]): the PAYLOAD instantiations, the plant carries it on its trunk (units k_rollout_pl, k_rollout_track_pl)
-template <class T> hipError_t k_rollout(const LaunchCtx& L, bool observer, bool track, int spw, const DevModel<T>* model, const DevParams<T>& prm,
-                                       const SweepArgs<T>& a, const QpArgs<T>& qa, const QpJidx& jmap, const IntegrateArgs<T>& ia, int horizon,
-                                       const DevRefParams<T>* G, const RefArgs<T>& ra, bool warm = false, const T* payload = nullptr);
-// rollout_scored_kernel<T, OBSERVER, TRACK, SPW, PAYLOAD>: k_rollout with the running cost accumulated on chip (score.hip.hpp; units k_rollout_sc*); always warm
-template <class T> hipError_t k_rollout_scored(const LaunchCtx& L, bool observer, bool track, int spw, const DevModel<T>* model, const DevParams<T>& prm,
-                                              const SweepArgs<T>& a, const QpArgs<T>& qa, const QpJidx& jmap, const IntegrateArgs<T>& ia, int horizon,
-                                              const DevRefParams<T>* G, const RefArgs<T>& ra, const T* payload, const ScoreArgs<T>& sc);
+// The rollout family: `horizon` dependent ticks incl. forward dynamics as one launch, rollout_kernel<T, OBSERVER, TRACK, SPW, WARM, PAYLOAD> or -- with the
+// running cost accumulated on chip (score.hip.hpp), always warm -- rollout_scored_kernel<T, OBSERVER, TRACK, SPW, PAYLOAD>.  What one launch carries:
+template <class T> struct RolloutLaunch {
+  bool observer; int spw;   // states per workgroup, 4 | 16
+  const DevModel<T>* model; DevParams<T> prm;
+  SweepArgs<T> a; QpArgs<T> qa; QpJidx jmap; IntegrateArgs<T> ia; int horizon;
+  const DevRefParams<T>* G; RefArgs<T> ra;   // ra.plan non-null: TRACK, the planner in the loop
+  bool warm;                                 // the unscored kernels' WARM
+  const T* payload;                          // non-null, [10][N]: PAYLOAD, the plant carries it on its trunk
+  const ScoreArgs<T>* score;                 // non-null: the scored kernels
+};
+// one variant's launcher; k_rollout.hip compiled with the variant's flags defines it (csrc/Makefile, ROLLOUT_UNITS)
+template <class T, bool TRACK, bool PAYLOAD, bool SCORE> hipError_t rollout_launch(const LaunchCtx& L, const RolloutLaunch<T>& r);
+// picks the variant from r.ra.plan, r.payload, r.score
+template <class T> hipError_t k_rollout(const LaunchCtx& L, const RolloutLaunch<T>& r);
 // score_tick_kernel<T>: one tick's cost l_k of every state into sc.cost / sc.fail (the per-tick path of the scored rollouts, wbc_score_batch)
 template <class T> hipError_t k_score_tick(const LaunchCtx& L, const ScoreArgs<T>& sc, const T* q, const T* v, const T* tau, const T* f, const int* status, int is_last);
 // rollout_select_kernel<T, BLOCK>: per group of `group` consecutive costs the best index, its cost and the MPPI weights (one workgroup per group)

@@ -838,7 +838,7 @@ extern "C" int wbc_solver_collect_timing(wbc_solver* s, double* ms, int* launche
     if (sc_.err != hipSuccess) return fail(WBC_E_HIP, std::string("hipEventRecord: ") + hipGetErrorString(sc_.err)); \
     const LaunchCtx& L = sc_.L;                                                                             \
     hipError_t le_ = (call_);                                                                               \
-    if (le_ != hipSuccess) { sc_.cancel(); return fail(WBC_E_HIP, std::string(what_ " launch: ") + hipGetErrorString(le_)); } \
+    if (le_ != hipSuccess) { sc_.cancel(); return fail(WBC_E_HIP, std::string(what_) + " launch: " + hipGetErrorString(le_)); } \
     le_ = sc_.end();                                                                                        \
     if (le_ != hipSuccess) return fail(WBC_E_HIP, std::string("hipEventRecord: ") + hipGetErrorString(le_)); \
   } while (0)
@@ -857,6 +857,47 @@ struct KeepScope {
   void written() { if (M) { s->kept_M = M; s->kept_Jc = Jc; s->kept_N = N; } done = true; }
   ~KeepScope() { if (M && !done) s->kept_M = nullptr; }
 };
+
+// ---- the kernels' argument structs from the C-ABI's: ONE builder each, filled in place; a caller then sets only the fields in which it differs
+template <class T>
+static void sweep_args(SweepArgs<T>& a, const wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs) {
+  std::memset(&a, 0, sizeof(a));
+  a.jpack = s->jpack;
+  a.N = N; a.q = (const T*)in->q; a.v = (const T*)in->v;
+  a.M = (T*)out->M; a.h = (T*)out->h; a.Jc = (T*)out->Jc; a.pf = (T*)out->pf;
+  a.w_des = (const T*)in->w_des; a.vdot_des = (const T*)in->vdot_des;
+  a.tau_prev = (const T*)in->tau_prev; a.f_prev = (const T*)in->f_prev;
+  a.obs_integ = obs ? (T*)obs->integ : nullptr; a.obs_r = obs ? (T*)obs->r : nullptr;
+  a.ws = (T*)s->d_ws;
+}
+// (Jc, wdes, aset_in, aset_out: null; rprev: the observer state where the observer runs)
+template <class T>
+static void qp_args(QpArgs<T>& qa, const wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs) {
+  std::memset(&qa, 0, sizeof(qa));
+  qa.jpack = s->jpack;
+  qa.N = N; qa.ws = (const T*)s->d_ws; qa.normals = (const T*)in->normals; qa.mu = (const T*)in->mu; qa.mask = in->mask;
+  qa.tau = (T*)out->tau; qa.f = (T*)out->f; qa.status = out->status; qa.iters = out->iters;
+  qa.rprev = (s->params.observer_order > 0 && obs) ? (const T*)obs->r : nullptr;
+}
+// (the integrator's public entry points take bare pointers, so this one does too)
+template <class T>
+static void integrate_args(IntegrateArgs<T>& a, const wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
+                           const void* tau, const void* f, const void* tau_ext, void* tau_traj) {
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.q = (T*)q; a.v = (T*)v; a.M = (const T*)M; a.h = (const T*)h; a.Jc = (const T*)Jc;
+  a.tau = (const T*)tau; a.f = (const T*)f; a.tau_ext = (const T*)tau_ext; a.tau_traj = (T*)tau_traj;
+  a.dt = (T)s->params.dt;
+  a.jpack = s->jpack;
+}
+// (simg, refimg, planimg, skip_out: set by the rollout kernel only)
+template <class T>
+static void ref_args(RefArgs<T>& a, const wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, double t, void* w_des,
+                     void* vdot_des, void* com) {
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.plan = (const T*)plan; a.t = (T)t;
+  a.w_des = (T*)w_des; a.vdot_des = (T*)vdot_des; a.com = (T*)com;
+  a.jpack = s->jpack;
+}
 
 template <class T>
 static int dynamics_impl(wbc_solver* s, size_t N, const void* q, const void* v, void* M, void* h, void* Jc, void* pf,
@@ -892,27 +933,16 @@ template <class T>
 static int step_impl(wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out,
                      const wbc_observer_state* obs, hipStream_t st, bool warm_api = false, const int* aset_in = nullptr, int* aset_out = nullptr) {
   SweepArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.jpack = s->jpack;
-  a.N = N; a.q = (const T*)in->q; a.v = (const T*)in->v;
-  a.M = (T*)out->M; a.h = (T*)out->h; a.Jc = (T*)out->Jc; a.pf = (T*)out->pf;
-  a.w_des = (const T*)in->w_des; a.vdot_des = (const T*)in->vdot_des;
-  a.tau_prev = (const T*)in->tau_prev; a.f_prev = (const T*)in->f_prev;
-  a.obs_integ = obs ? (T*)obs->integ : nullptr; a.obs_r = obs ? (T*)obs->r : nullptr;
-  a.ws = (T*)s->d_ws;
+  sweep_args(a, s, N, in, out, obs);
   const bool mats = out->M != nullptr, ob = s->params.observer_order > 0;
   KeepScope keep(s, out->M, out->Jc, N);
   a.skip_consts = keep.skip;
   timing_tick(s);
   QpArgs<T> qa;
-  qa.jpack = s->jpack;
-  qa.N = N; qa.ws = (const T*)s->d_ws; qa.normals = (const T*)in->normals; qa.mu = (const T*)in->mu; qa.mask = in->mask;
-  qa.tau = (T*)out->tau; qa.f = (T*)out->f; qa.status = out->status; qa.iters = out->iters;
+  qp_args(qa, s, N, in, out, obs);
   qa.aset_in = aset_in; qa.aset_out = aset_out;
-  qa.rprev = (ob && obs) ? (const T*)obs->r : nullptr;
   // two-kernel tick with M/h/Jc outputs: the QP takes its geometry from Jc and the sweep skips those workspace words
   qa.Jc = mats ? (const T*)out->Jc : nullptr;
-  qa.wdes = nullptr;
   a.ws_geom = mats ? 0 : 1;
   const DevParams<T> dp = to_dev_params<T>(s->params);
   // (what runs, and why: plan_tick.  A warm call WITHOUT a set to start from -- tick 0 of a per-tick-launch rollout, the first tick of a closed loop --
@@ -1035,11 +1065,7 @@ template <class T>
 static int integrate_impl(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
                           const void* tau, const void* f, const void* tau_ext, void* tau_traj, hipStream_t st, const void* payload = nullptr) {
   IntegrateArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.N = N; a.q = (T*)q; a.v = (T*)v; a.M = (const T*)M; a.h = (const T*)h; a.Jc = (const T*)Jc;
-  a.tau = (const T*)tau; a.f = (const T*)f; a.tau_ext = (const T*)tau_ext; a.tau_traj = (T*)tau_traj;
-  a.dt = (T)s->params.dt;
-  a.jpack = s->jpack;
+  integrate_args(a, s, N, q, v, M, h, Jc, tau, f, tau_ext, tau_traj);
   LaunchCtx L; L.st = st;
   hipError_t e = payload ? k_integrate_plant<T>(L, dev_model<T>(s), a, (const T*)payload) : k_integrate<T>(L, dev_model<T>(s), a);
   if (e != hipSuccess) return fail(WBC_E_HIP, std::string("integrate launch: ") + hipGetErrorString(e));
@@ -1116,66 +1142,64 @@ static int score_tick(wbc_solver* s, size_t N, const void* q, const void* v, con
   return WBC_OK;
 }
 
-// small batches: the whole horizon in ONE launch (rollout_kernel, fused_tick.hip.hpp)
+// ---- the rollout family: what a call carries beyond the tick's batch structs, all of it optional; the entry points fill it
+struct RolloutExtras {
+  const void* tau_ext = nullptr;             // [nv][N] external torques on the plant
+  const void* payload = nullptr;             // the plant's trunk carries it, in the persistent kernel and in the per-tick integrate launches alike
+  const void* plan = nullptr;                // non-null: the planner in the loop, w_des / vdot_des are regenerated every tick
+  void* tau_traj = nullptr;                  // [horizon][nj][N]
+  void* com_traj = nullptr;                  // [horizon][6][N] (the planner records it)
+  const wbc_rollout_score* score = nullptr;  // non-null (and through score_arg_check): the running cost is accumulated
+};
+
+// small batches: the whole horizon in ONE launch (rollout_kernel / rollout_scored_kernel, fused_tick.hip.hpp); in->tau_prev / f_prev are out's tau / f
 template <class T>
 static int rollout_persistent(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
-                              const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, hipStream_t st,
-                              const void* plan = nullptr, void* com_traj = nullptr, const void* payload = nullptr, const wbc_rollout_score* score = nullptr) {
-  SweepArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.jpack = s->jpack;
-  a.N = N; a.q = (const T*)in->q; a.v = (const T*)in->v;
-  a.M = (T*)out->M; a.h = (T*)out->h; a.Jc = (T*)out->Jc; a.pf = (T*)out->pf;
-  a.w_des = (const T*)in->w_des; a.vdot_des = (const T*)in->vdot_des;
-  a.tau_prev = (const T*)out->tau; a.f_prev = (const T*)out->f;
-  a.obs_integ = obs ? (T*)obs->integ : nullptr; a.obs_r = obs ? (T*)obs->r : nullptr;
-  a.ws = (T*)s->d_ws;
-  a.skip_consts = 0;   // (tick 0 writes M / Jc in full; the later ticks of the launch leave their structural zeros / ones alone: rollout_kernel)
+                              const wbc_observer_state* obs, const RolloutExtras& x, hipStream_t st) {
+  RolloutLaunch<T> r;
+  sweep_args(r.a, s, N, in, out, obs);
+  r.a.skip_consts = 0;   // (tick 0 writes M / Jc in full; the later ticks of the launch leave their structural zeros / ones alone: rollout_kernel)
+  r.a.ws_geom = 1;
   s->kept_M = nullptr;
-  QpArgs<T> qa;
-  qa.jpack = s->jpack;
-  qa.N = N; qa.ws = (const T*)s->d_ws; qa.normals = (const T*)in->normals; qa.mu = (const T*)in->mu; qa.mask = in->mask;
-  qa.tau = (T*)out->tau; qa.f = (T*)out->f; qa.status = out->status; qa.iters = out->iters; qa.Jc = nullptr; qa.wdes = nullptr;
-  qa.aset_in = nullptr; qa.aset_out = nullptr;   // (every tick of the launch but the first starts from the previous tick's set, kept in registers)
+  qp_args(r.qa, s, N, in, out, obs);   // (aset_in null: every tick of the launch but the first starts from the previous tick's set, kept in registers)
   // (cold rollouts with the planner in the loop keep the QP waiting for rhat: the speculative start lost there, 26.8 -> 29.0 us per tick)
-  qa.rprev = (s->params.observer_order > 0 && obs && !plan) ? (const T*)obs->r : nullptr;
-  a.ws_geom = 1;
-  IntegrateArgs<T> ia;
-  std::memset(&ia, 0, sizeof(ia));
-  ia.N = N; ia.q = (T*)in->q; ia.v = (T*)in->v; ia.M = (const T*)out->M; ia.h = (const T*)out->h; ia.Jc = (const T*)out->Jc;
-  ia.tau = (const T*)out->tau; ia.f = (const T*)out->f; ia.tau_ext = (const T*)tau_ext; ia.tau_traj = (T*)tau_traj;
-  ia.dt = (T)s->params.dt;
-  ia.jpack = s->jpack;
+  if (x.plan) r.qa.rprev = nullptr;
+  integrate_args(r.ia, s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, x.tau_ext, x.tau_traj);
+  ref_args(r.ra, s, N, in->q, in->v, x.plan, 0.0, (void*)in->w_des, (void*)in->vdot_des, x.com_traj);
+  r.observer = s->params.observer_order > 0;
   // states per workgroup: 4 while that still fits one workgroup per CU (a tick then waits for the slowest of 4 QPs, not 16)
-  const int spw = (s->opt.rollout_spw == 4 || (s->opt.rollout_spw == 0 && N <= 1024)) ? 4 : 16;
-  RefArgs<T> ra;
-  std::memset(&ra, 0, sizeof(ra));
-  ra.jpack = s->jpack;
-  ra.N = N; ra.q = (const T*)in->q; ra.v = (const T*)in->v; ra.plan = (const T*)plan; ra.t = (T)0;
-  ra.w_des = (T*)in->w_des; ra.vdot_des = (T*)in->vdot_des; ra.com = (T*)com_traj;
+  r.spw = (s->opt.rollout_spw == 4 || (s->opt.rollout_spw == 0 && N <= 1024)) ? 4 : 16;
+  r.model = dev_model<T>(s); r.prm = to_dev_params<T>(s->params); r.jmap = s->jmap; r.horizon = horizon;
+  r.G = (const DevRefParams<T>*)s->d_ref;
+  r.warm = x.score || s->opt.rollout_warm != 0;   // (the scored kernels are always warm)
+  r.payload = (const T*)x.payload;
+  ScoreArgs<T> sc;
+  if (x.score) sc = score_args<T>(s, N, x.score, x.score->accumulate != 0);
+  r.score = x.score ? &sc : nullptr;
   timing_tick(s);
-  if (score) {   // the scored sibling of the same kernel (always warm)
-    const ScoreArgs<T> sc = score_args<T>(s, N, score, score->accumulate != 0);
-    TIMED_LAUNCH(5, st, "scored rollout", k_rollout_scored<T>(L, s->params.observer_order > 0, plan != nullptr, spw, dev_model<T>(s), to_dev_params<T>(s->params), a, qa,
-                                                              s->jmap, ia, horizon, (const DevRefParams<T>*)s->d_ref, ra, (const T*)payload, sc));
-    return WBC_OK;
-  }
-  TIMED_LAUNCH(5, st, "rollout", k_rollout<T>(L, s->params.observer_order > 0, plan != nullptr, spw, dev_model<T>(s), to_dev_params<T>(s->params), a, qa,
-                                              s->jmap, ia, horizon, (const DevRefParams<T>*)s->d_ref, ra, s->opt.rollout_warm != 0, (const T*)payload));
+  TIMED_LAUNCH(5, st, x.score ? "scored rollout" : "rollout", k_rollout<T>(L, r));
   return WBC_OK;
 }
 
 static bool rollout_as_one_launch(const wbc_solver* s, size_t N) { return N <= s->rz.fused_max && s->opt.rollout_persistent; }
 
-// wbc_rollout_batch; payload (wbc_rollout_plant_batch): the plant's trunk carries it, in the persistent kernel and in the per-tick integrate launches alike
-static int rollout_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
-                        const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, void* stream, const void* payload,
-                        const wbc_rollout_score* score = nullptr) {
+// every wbc_rollout_*_batch: one launch, or per tick [reference] -> step (warm or cold) -> integrate -> [score]
+static int rollout(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs,
+                   const RolloutExtras& x, void* stream) {
   if (!s || !in || !out) return fail(WBC_E_INVALID, "null argument");
   if (horizon < 1) return fail(WBC_E_INVALID, "horizon must be >= 1");
-  if (score && !out->status) return fail(WBC_E_INVALID, "scored rollouts need the status buffer");
+  if (x.score && !out->status) return fail(WBC_E_INVALID, "scored rollouts need the status buffer");
   if (!out->M || !out->h || !out->Jc) return fail(WBC_E_INVALID, "rollouts need the M, h, Jc buffers (forward dynamics reads them)");
+  if (x.plan) {
+    if (!in->q || !in->v || !in->w_des || !in->vdot_des) return fail(WBC_E_INVALID, "null input buffer");
+    if (!s->d_ref) return fail(WBC_E_INVALID, "call wbc_solver_set_ref_params first");
+  }
   if (N == 0) return WBC_OK;   // empty shard
+  wbc_batch_in tick = *in;
+  tick.tau_prev = out->tau;  // the previous tick's outputs are this tick's tau_prev / f_prev: the sweep reads them
+  tick.f_prev = out->f;      // before the QP kernel of the same tick overwrites them
+  const bool f64 = s->dtype == WBC_F64;
+  hipStream_t st = (hipStream_t)stream;
   if (rollout_as_one_launch(s, N)) {
     if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
     if (!in->q || !in->v || !in->w_des || !in->vdot_des || !in->normals || !in->mu || !in->mask)
@@ -1184,35 +1208,35 @@ static int rollout_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in
     if (s->params.observer_order > 0 && (!obs || !obs->integ || !obs->r))
       return fail(WBC_E_INVALID, "observer on: observer state buffers required");
     ON_DEVICE(s);
-    hipStream_t st0 = (hipStream_t)stream;
-    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, nullptr, nullptr, payload, score)
-                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, nullptr, nullptr, payload, score);
+    return f64 ? rollout_persistent<double>(s, N, horizon, &tick, out, obs, x, st) : rollout_persistent<float>(s, N, horizon, &tick, out, obs, x, st);
   }
-  wbc_batch_in tick = *in;
-  tick.tau_prev = out->tau;  // the previous tick's outputs are this tick's tau_prev / f_prev: the sweep reads them
-  tick.f_prev = out->f;      // before the QP kernel of the same tick overwrites them
-  const size_t ts = s->dtype == WBC_F64 ? 8 : 4;
+  // (per-tick launches: wbc_step_batch checks the buffers)
+  const size_t ts = f64 ? 8 : 4;
   const size_t nj = 12;
   ON_DEVICE(s);
-  s->kept_M = nullptr;   // tick 0 writes M, Jc in full whatever an earlier call left there
   // rollout_warm with per-tick launches: where the planner's warm tick really starts from the sets (fused launch, warm one-wavefront kernel,
   // warm per-lane pair); in between the cold tiles are the faster kernels (plan_tick)
   const bool warm_ticks = s->opt.rollout_warm && plan_tick(s->dtype, s->params.observer_order, s->opt, s->rz, N, true, out->pf != nullptr, true).qp_warm;
   for (int t = 0; t < horizon; ++t) {
+    int rc;
+    if (x.plan) {
+      void* com = x.com_traj ? (void*)((char*)x.com_traj + (size_t)t * 6 * N * ts) : nullptr;
+      rc = wbc_reference_batch(s, N, in->q, in->v, x.plan, (double)t * s->params.dt, (void*)in->w_des, (void*)in->vdot_des, com, stream);
+      if (rc) return rc;
+    }
+    if (t == 0) s->kept_M = nullptr;   // tick 0 writes M, Jc in full whatever an earlier call left there
     s->in_rollout = t > 0;
     // tick t > 0 starts its QPs from the active sets tick t - 1 left in d_aset
-    int rc = warm_ticks ? wbc_step_batch_warm(s, N, &tick, out, obs, t > 0 ? s->d_aset : nullptr, s->d_aset, stream)
-                                 : wbc_step_batch(s, N, &tick, out, obs, stream);
+    rc = warm_ticks ? wbc_step_batch_warm(s, N, &tick, out, obs, t > 0 ? s->d_aset : nullptr, s->d_aset, stream)
+                    : wbc_step_batch(s, N, &tick, out, obs, stream);
     s->in_rollout = 0;
     if (rc) return rc;
-    void* traj = tau_traj ? (void*)((char*)tau_traj + (size_t)t * nj * N * ts) : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    rc = s->dtype == WBC_F64
-             ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload)
-             : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload);
+    void* traj = x.tau_traj ? (void*)((char*)x.tau_traj + (size_t)t * nj * N * ts) : nullptr;
+    rc = f64 ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, x.tau_ext, traj, st, x.payload)
+             : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, x.tau_ext, traj, st, x.payload);
     if (rc) return rc;
-    if (score) {
-      rc = score_tick(s, N, in->q, in->v, out->tau, out->f, out->status, score, t > 0 || score->accumulate != 0, t == horizon - 1, st);
+    if (x.score) {
+      rc = score_tick(s, N, in->q, in->v, out->tau, out->f, out->status, x.score, t > 0 || x.score->accumulate != 0, t == horizon - 1, st);
       if (rc) return rc;
     }
   }
@@ -1221,15 +1245,39 @@ static int rollout_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in
 
 extern "C" int wbc_rollout_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
                                  const wbc_observer_state* obs, const void* tau_ext, void* tau_traj, void* stream) {
-  return rollout_impl(s, N, horizon, in, out, obs, tau_ext, tau_traj, stream, nullptr);
+  RolloutExtras x;
+  x.tau_ext = tau_ext; x.tau_traj = tau_traj;
+  return rollout(s, N, horizon, in, out, obs, x, stream);
 }
 
 extern "C" int wbc_rollout_plant_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
                                        const wbc_observer_state* obs, const wbc_plant* plant, void* tau_traj, void* stream) {
-  const void *tau_ext, *payload;
-  const int rc = plant_args(plant, &tau_ext, &payload);
+  RolloutExtras x;
+  const int rc = plant_args(plant, &x.tau_ext, &x.payload);
   if (rc) return rc;
-  return rollout_impl(s, N, horizon, in, out, obs, tau_ext, tau_traj, stream, payload);
+  x.tau_traj = tau_traj;
+  return rollout(s, N, horizon, in, out, obs, x, stream);
+}
+
+// (the planner's entry points refuse a call without a plan: to rollout() a null plan is the call without the planner)
+extern "C" int wbc_rollout_tracking_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in,
+                                          const wbc_batch_out* out, const wbc_observer_state* obs, const void* tau_ext,
+                                          const void* plan, void* tau_traj, void* com_traj, void* stream) {
+  if (!plan) return fail(WBC_E_INVALID, "null argument");
+  RolloutExtras x;
+  x.tau_ext = tau_ext; x.plan = plan; x.tau_traj = tau_traj; x.com_traj = com_traj;
+  return rollout(s, N, horizon, in, out, obs, x, stream);
+}
+
+extern "C" int wbc_rollout_tracking_plant_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
+                                                const wbc_observer_state* obs, const wbc_plant* plant, const void* plan, void* tau_traj,
+                                                void* com_traj, void* stream) {
+  RolloutExtras x;
+  const int rc = plant_args(plant, &x.tau_ext, &x.payload);
+  if (rc) return rc;
+  if (!plan) return fail(WBC_E_INVALID, "null argument");
+  x.plan = plan; x.tau_traj = tau_traj; x.com_traj = com_traj;
+  return rollout(s, N, horizon, in, out, obs, x, stream);
 }
 
 // ------------------------------------------------------------------------------------------ CoM reference generator
@@ -1267,10 +1315,7 @@ template <class T>
 static int reference_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, double t, void* w_des,
                           void* vdot_des, void* com, hipStream_t st) {
   RefArgs<T> a;
-  std::memset(&a, 0, sizeof(a));   // (simg, refimg, planimg, skip_out: set by the rollout kernel only -- ADVICE r5)
-  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.plan = (const T*)plan; a.t = (T)t;
-  a.w_des = (T*)w_des; a.vdot_des = (T*)vdot_des; a.com = (T*)com;
-  a.jpack = s->jpack;
+  ref_args(a, s, N, q, v, plan, t, w_des, vdot_des, com);
   LaunchCtx L; L.st = st;
   hipError_t e = k_reference<T>(L, dev_model<T>(s), (const DevRefParams<T>*)s->d_ref, a);
   if (e != hipSuccess) return fail(WBC_E_HIP, std::string("reference launch: ") + hipGetErrorString(e));
@@ -1287,74 +1332,6 @@ extern "C" int wbc_reference_batch(wbc_solver* s, size_t N, const void* q, const
   hipStream_t st = (hipStream_t)stream;
   return s->dtype == WBC_F64 ? reference_impl<double>(s, N, q, v, plan, t, w_des, vdot_des, com, st)
                              : reference_impl<float>(s, N, q, v, plan, t, w_des, vdot_des, com, st);
-}
-
-static int rollout_tracking_impl(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
-                                 const wbc_observer_state* obs, const void* tau_ext, const void* plan, void* tau_traj, void* com_traj,
-                                 void* stream, const void* payload, const wbc_rollout_score* score = nullptr) {
-  if (!s || !in || !out || !plan) return fail(WBC_E_INVALID, "null argument");
-  if (horizon < 1) return fail(WBC_E_INVALID, "horizon must be >= 1");
-  if (score && !out->status) return fail(WBC_E_INVALID, "scored rollouts need the status buffer");
-  if (!out->M || !out->h || !out->Jc) return fail(WBC_E_INVALID, "rollouts need the M, h, Jc buffers (forward dynamics reads them)");
-  if (!in->q || !in->v || !in->w_des || !in->vdot_des) return fail(WBC_E_INVALID, "null input buffer");
-  if (!s->d_ref) return fail(WBC_E_INVALID, "call wbc_solver_set_ref_params first");
-  if (N == 0) return WBC_OK;   // empty shard
-  if (rollout_as_one_launch(s, N)) {
-    if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-    if (!in->normals || !in->mu || !in->mask) return fail(WBC_E_INVALID, "null input buffer");
-    if (!out->tau || !out->f || !out->status) return fail(WBC_E_INVALID, "null output buffer");
-    if (s->params.observer_order > 0 && (!obs || !obs->integ || !obs->r))
-      return fail(WBC_E_INVALID, "observer on: observer state buffers required");
-    ON_DEVICE(s);
-    hipStream_t st0 = (hipStream_t)stream;
-    return s->dtype == WBC_F64 ? rollout_persistent<double>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj, payload, score)
-                               : rollout_persistent<float>(s, N, horizon, in, out, obs, tau_ext, tau_traj, st0, plan, com_traj, payload, score);
-  }
-  wbc_batch_in tick = *in;
-  tick.tau_prev = out->tau;
-  tick.f_prev = out->f;
-  const size_t ts = s->dtype == WBC_F64 ? 8 : 4;
-  const size_t nj = 12;
-  ON_DEVICE(s);
-  const bool warm_ticks = s->opt.rollout_warm && plan_tick(s->dtype, s->params.observer_order, s->opt, s->rz, N, true, out->pf != nullptr, true).qp_warm;
-  for (int t = 0; t < horizon; ++t) {
-    void* com = com_traj ? (void*)((char*)com_traj + (size_t)t * 6 * N * ts) : nullptr;
-    int rc = wbc_reference_batch(s, N, in->q, in->v, plan, (double)t * s->params.dt, (void*)in->w_des, (void*)in->vdot_des, com,
-                                 stream);
-    if (rc) return rc;
-    if (t == 0) s->kept_M = nullptr;
-    s->in_rollout = t > 0;
-    rc = warm_ticks ? wbc_step_batch_warm(s, N, &tick, out, obs, t > 0 ? s->d_aset : nullptr, s->d_aset, stream)
-                             : wbc_step_batch(s, N, &tick, out, obs, stream);
-    s->in_rollout = 0;
-    if (rc) return rc;
-    void* traj = tau_traj ? (void*)((char*)tau_traj + (size_t)t * nj * N * ts) : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    rc = s->dtype == WBC_F64
-             ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload)
-             : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, tau_ext, traj, st, payload);
-    if (rc) return rc;
-    if (score) {
-      rc = score_tick(s, N, in->q, in->v, out->tau, out->f, out->status, score, t > 0 || score->accumulate != 0, t == horizon - 1, st);
-      if (rc) return rc;
-    }
-  }
-  return WBC_OK;
-}
-
-extern "C" int wbc_rollout_tracking_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in,
-                                          const wbc_batch_out* out, const wbc_observer_state* obs, const void* tau_ext,
-                                          const void* plan, void* tau_traj, void* com_traj, void* stream) {
-  return rollout_tracking_impl(s, N, horizon, in, out, obs, tau_ext, plan, tau_traj, com_traj, stream, nullptr);
-}
-
-extern "C" int wbc_rollout_tracking_plant_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
-                                                const wbc_observer_state* obs, const wbc_plant* plant, const void* plan, void* tau_traj,
-                                                void* com_traj, void* stream) {
-  const void *tau_ext, *payload;
-  const int rc = plant_args(plant, &tau_ext, &payload);
-  if (rc) return rc;
-  return rollout_tracking_impl(s, N, horizon, in, out, obs, tau_ext, plan, tau_traj, com_traj, stream, payload);
 }
 
 // ---- scored rollouts: the weights, the superset rollout, one tick's cost, the per-group selection
@@ -1381,17 +1358,14 @@ extern "C" int wbc_solver_set_score_params(wbc_solver* s, const wbc_score_params
 extern "C" int wbc_rollout_scored_batch(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in, const wbc_batch_out* out,
                                         const wbc_observer_state* obs, const wbc_plant* plant, const void* plan, void* tau_traj, void* com_traj,
                                         const wbc_rollout_score* score, void* stream) {
-  const wbc_rollout_score* use;
-  int rc = score_arg_check(score, &use);
+  RolloutExtras x;
+  int rc = score_arg_check(score, &x.score);
   if (rc) return rc;
-  const void *tau_ext, *payload;
-  rc = plant_args(plant, &tau_ext, &payload);
+  rc = plant_args(plant, &x.tau_ext, &x.payload);
   if (rc) return rc;
-  if (!plan) {
-    if (com_traj) return fail(WBC_E_INVALID, "com_traj needs a plan (the planner records it)");
-    return rollout_impl(s, N, horizon, in, out, obs, tau_ext, tau_traj, stream, payload, use);
-  }
-  return rollout_tracking_impl(s, N, horizon, in, out, obs, tau_ext, plan, tau_traj, com_traj, stream, payload, use);
+  if (!plan && com_traj) return fail(WBC_E_INVALID, "com_traj needs a plan (the planner records it)");
+  x.plan = plan; x.tau_traj = tau_traj; x.com_traj = com_traj;
+  return rollout(s, N, horizon, in, out, obs, x, stream);
 }
 
 extern "C" int wbc_score_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* tau, const void* f, const int* status,
