@@ -6,6 +6,11 @@
 #   tools/ab_libs.sh loops "<sizes>" libA libB ...         tools/warm_loop.py with WARM_LOOP_LANE=1: cold / warm without the per-lane pair / warm per-lane pair / warm
 #                                                           one-wavefront kernel forced, per size and workload
 #   tools/ab_libs.sh tests "<pytest args>" libA ...        the GPU tests against a library build
+#   tools/ab_libs.sh plain "<bench args>" libA libB ...    the PLAIN bench.py run (what the headline is), builds alternating, REPS (default 5) runs each; then
+#                                                           median and min - max of `value` per build, and the gain rule (first item): it is a gain only
+#                                                           if the two ranges do not overlap and the median gain is at least three times the first build's own
+#                                                           min - max spread.  What bench.py writes to stderr is kept in ab_libs_plain.err beside the working directory's
+#                                                           other output (AB_ERR to put it elsewhere)
 set -u
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
@@ -16,6 +21,28 @@ if [ "$what" = "loops" ]; then
     echo "== $L"
     WBC_LIB=$PWD/wbc_quadruped_dob_amd/$L/libwbc_hip.so WARM_LOOP_LANE=1 timeout 1500 python tools/warm_loop.py $sizes 2>/dev/null
   done
+  exit 0
+fi
+if [ "$what" = "plain" ]; then
+  pargs="$1"; shift
+  vals=$(mktemp); trap 'rm -f "$vals"' EXIT
+  err=${AB_ERR:-$PWD/ab_libs_plain.err}; : > "$err"
+  for rep in $(seq 1 ${REPS:-5}); do for L in "$@"; do
+    v=$(WBC_LIB=$PWD/wbc_quadruped_dob_amd/$L/libwbc_hip.so timeout -k 10 300 python bench.py $pargs 2>> "$err" | python -c 'import sys, json; print("%.3f" % (json.loads(sys.stdin.read())["value"] / 1e6))') || { echo "bench.py failed: $L rep $rep (stderr: $err)"; tail -5 "$err"; exit 1; }
+    echo "$L [$pargs] rep $rep  $v M/s"; echo "$L $v" >> $vals
+  done; done
+  python - $vals "$@" <<'PY'
+import sys, statistics
+rows = [l.split() for l in open(sys.argv[1])]
+base = None
+for L in sys.argv[2:]:
+    v = sorted(float(x) for n, x in rows if n == L)
+    med = statistics.median(v)
+    line = "%-24s median %8.2f M/s   min - max %8.2f - %8.2f (spread %.2f)" % (L, med, v[0], v[-1], v[-1] - v[0])
+    if base is None: base = (med, v[0], v[-1])
+    else: line += "   vs %s: %+.2f %%, ranges %s, gain / its spread %.1f" % (sys.argv[2], 100 * (med / base[0] - 1), "overlap" if v[0] <= base[2] and base[1] <= v[-1] else "apart", (med - base[0]) / max(base[2] - base[1], 1e-9))
+    print(line)
+PY
   exit 0
 fi
 if [ "$what" = "tests" ]; then

@@ -9,6 +9,32 @@
 
 namespace wbc {
 
+// ---- cache policy of pure-output stores (M, h, Jc, pf: words nobody on the GPU reads back inside the launch) -------------------------
+// ST_PLAIN: the line stays dirty in the XCD's L2 until something evicts it -- at the latest the write-back at the end of the kernel.
+// ST_WT: write-through at agent scope (`sc1`): the bytes leave L2 while the kernel is still running and the line is dropped.  The one-launch tick leaves 14 MB of
+// outputs per launch at 4 096 fp64 states; stored plainly they sat in L2 through the whole QP tail and their write-back was about 1 us behind the last instruction
+// (DESIGN.md 7).  Only for words no wavefront of the launch loads again.
+// A compile-time parameter of the bodies that store outputs (dyn_split.hip.hpp: the template parameter STP of mass_jac_body and structural_consts_quarter, the mode bit RS_WT
+// of rnea_step_body, whose parameter list ends in deduced hook types).  Every kernel that does not opt in keeps ST_PLAIN, and ST_PLAIN never comes through store_out: the
+// bodies keep their plain assignment in place (WBC_ST), because the same store routed through a function came out of the compiler in another order.
+constexpr int ST_PLAIN = 0, ST_WT = 1;
+#if defined(__HIP__)
+template <int POLICY, class V> WBC_DEV void store_out(V* p, V v) {
+  static_assert(POLICY == ST_WT, "store_out: write-through only; plain stores stay plain assignments in the bodies");
+  if constexpr (sizeof(V) == 16) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    // 16 bytes: inline assembly, because no builtin gives `global_store_dwordx4 ... sc1`.  __hip_atomic_store stops at 8 bytes on this target (16: "exceeds the max
+    // lock-free size", an error), and __builtin_nontemporal_store sets `nt`, which keeps the line in L2 (measured: 322 M steps/s against 340 M, docs/DESIGN_HISTORY.md).
+    // The s_nop: on gfx9 a store of more than 8 bytes needs two wait states before a VALU instruction may overwrite its data registers; the compiler's hazard pass
+    // inserts them for its own stores and does not look into inline assembly.
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(__builtin_bit_cast(u32x4, v)) : "memory");
+  } else {
+    static_assert(sizeof(V) == 8, "store_out: a double or a pair of doubles (fp32 ticks keep plain stores: fused_tick.hip.hpp)");
+    __hip_atomic_store((unsigned long long*)p, __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+#endif
+
 // ---- per-leg model constants, as read by the dynamics-sweep kernel -------------------------
 // Table layout in memory: cst[idx * 4 + leg]; one lane owns one leg, so a wave reads four
 // distinct consecutive words per table row (conflict-free in LDS).
@@ -178,6 +204,7 @@ constexpr int RS_REFIMG = 256; // (role with RS_STEP, four-wavefront rollout wor
                                // image (SweepArgs::refimg), not from memory
 constexpr int RS_NOJC = 128; // (role with RS_STEP, four-wavefront rollout workgroups) the own-leg Jacobian blocks are NOT propagated up the return sweep and not written
                              // to WS_JCL: the QP's torque map takes them from the mass_jac role's LDS image, which is complete ~2 us before this role ends
+constexpr int RS_WT = 512;   // (role of the one-launch tick) pure outputs -- h -- are stored write-through: store_out<ST_WT>
 constexpr int RS_LANE2 = 64; // (roles with 4 states per workgroup, RS_STEP | RS_H) the two force recursions SIDE BY SIDE in the lanes instead of one after the
                              // other: slots 0 .. 3 of every leg row run RNEA(q, v, 0) (the bias forces h), slots 4 .. 7 RNEA(q, 0, vdot_des) without gravity
                              // (M vdot_des) of the same states, as ONE instruction stream; tau_partial = their sum, across lanes (round 5)

@@ -63,10 +63,13 @@ namespace wbc {
 // kernel, which sits at 256 registers, spills -- 19.5 -> 24.0 us per tick, measured)
 // -DWBC_ROLE_UNGUARD=1 (A/B): pure-output stores of the ROLES (EXT != 0) without their guard -- a dead lane of a role duplicates a state of its own wavefront
 #define WBC_ROLE_LIVE ((0 && EXT != 0) || live)
-#define STV(ptr, comp, val) do { if (WBC_ROLE_LIVE) *(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)
+// (pure outputs: the body names its policy STP; ST_PLAIN keeps the plain assignment as it always stood, so that the code of the kernels that do not opt in
+//  stays what it was -- routed through store_out<ST_PLAIN> the same stores came out of the compiler in another order, rollout kernels included)
+#define WBC_ST(T_, addr, val) do { if constexpr (STP == ST_PLAIN) *(T_*)(addr) = (val); else store_out<STP>((T_*)(addr), (T_)(val)); } while (0)
+#define STV(ptr, comp, val) do { if (WBC_ROLE_LIVE) WBC_ST(T, (char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T)), val); } while (0)
 #define STVG(ptr, comp, val) do { if (live) *(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)   /* in/out state (observer): dead lanes of OTHER wavefronts would race with the live one */
-#define STL(ptr, c0, stride, val) do { if (WBC_ROLE_LIVE) *(T*)((char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + s32) * (unsigned)sizeof(T))) = (val); } while (0)
-#define STLX(ptr, c0, stride, xN, val) do { if (WBC_ROLE_LIVE) *(T*)((char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + (xN) + s32) * (unsigned)sizeof(T))) = (val); } while (0)
+#define STL(ptr, c0, stride, val) do { if (WBC_ROLE_LIVE) WBC_ST(T, (char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + s32) * (unsigned)sizeof(T)), val); } while (0)
+#define STLX(ptr, c0, stride, xN, val) do { if (WBC_ROLE_LIVE) WBC_ST(T, (char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + (xN) + s32) * (unsigned)sizeof(T)), val); } while (0)
 #define ST4(ptr, c0, v0_, c1, v1_, c2, v2_, c3, v3_) STV(ptr, sel4<int>(leg, c0, c1, c2, c3), sel4<T>(leg, v0_, v1_, v2_, v3_))
 #define ST4G(ptr, c0, v0_, c1, v1_, c2, v2_, c3, v3_) STVG(ptr, sel4<int>(leg, c0, c1, c2, c3), sel4<T>(leg, v0_, v1_, v2_, v3_))
 #define MAKE_R(R_, qx, qy, qz, qw) do { const T x = qx, y = qy, z = qz, w = qw; \
@@ -90,7 +93,7 @@ constexpr int WBC_RS_WAVES = 2;
 // wavefronts are idle until the lever arms arrive: each takes a quarter of these stores there (wavefronts 0..2 one row of every
 // foot's Jc block, wavefront 3 the zeros of M), and the mass_jac role (ZEROS = false) is left with the data-dependent entries.
 // tx = thread index within the four QP wavefronts (0..255): state slot tx & 15, leg (tx >> 4) & 3, quarter tx >> 6.
-template <class T>
+template <class T, int STP = ST_PLAIN>
 WBC_DEV void structural_consts_quarter(const DevModel<T>* __restrict__ model, const SweepArgs<T>& a, const int* zidx_s, unsigned tx) {
   const size_t N = a.N;
   const unsigned N32 = (unsigned)N;
@@ -107,7 +110,7 @@ WBC_DEV void structural_consts_quarter(const DevModel<T>* __restrict__ model, co
     // ones, each for both states (as in dyn_sweep_kernel): half the store instructions
     struct alignas(2 * sizeof(T)) T2 { T a, b; };
     const unsigned odd = s32 & 1u, s2 = s32 & ~1u;
-#define ST2C(ptr, comp, val) do { if (live) *(T2*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s2) * (unsigned)sizeof(T))) = T2{(val), (val)}; } while (0)
+#define ST2C(ptr, comp, val) do { if (live) WBC_ST(T2, (char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s2) * (unsigned)sizeof(T)), (T2{(val), (val)})); } while (0)
     if (part == 3) {
       for (int e = 2 * leg + (int)odd; e < 64; e += 8) {
         const int zi = zidx_s[e];
@@ -126,7 +129,7 @@ WBC_DEV void structural_consts_quarter(const DevModel<T>* __restrict__ model, co
     }
 #undef ST2C
   } else {
-#define ST1C(ptr, comp, val) do { if (live) *(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)
+#define ST1C(ptr, comp, val) do { if (live) WBC_ST(T, (char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T)), val); } while (0)
     if (part == 3) {
       for (int e = leg; e < 64; e += 4) {
         const int zi = zidx_s[e];
@@ -156,7 +159,7 @@ WBC_DEV void structural_consts_quarter(const DevModel<T>* __restrict__ model, co
 // store instruction costs ~90 cycles to issue whatever its width (tools/issue_probe.hip): they were ~2 us of the mass_jac -> factorisation chain.
 constexpr int MJ_HAND_WORDS = 46;
 struct MjNoHook { WBC_DEV void operator()() const {} };
-template <class T, int BLOCK, int EXT, int SPW = 16, int ZEROS = 1, class AfterHand = MjNoHook>   // ZEROS: 0 = other wavefronts write the structural constants, 1 = first, 2 = LAST (behind the data: fused_tick.hip.hpp)
+template <class T, int BLOCK, int EXT, int SPW = 16, int ZEROS = 1, class AfterHand = MjNoHook, int STP = ST_PLAIN>   // STP: store_out policy of M, Jc, pf; ZEROS: 0 = other wavefronts write the structural constants, 1 = first, 2 = LAST (behind the data: fused_tick.hip.hpp)
 WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArgs<T>& a, const T* cst_ext, const int* zidx_ext, T* hand = nullptr,
                            AfterHand after_hand = AfterHand()) {
   static_assert(!EXT || BLOCK == 64 || BLOCK == 128, "one wavefront (128: one of the two role wavefronts of a fused_pair_kernel workgroup, each with its own half of the parking lot)");
@@ -410,6 +413,7 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
   WBC_LAUNDERED_TID(tx);
   constexpr bool WH = (MODE & RS_H) != 0, STEP = (MODE & RS_STEP) != 0, OBS = (MODE & RS_OBS) != 0, WPF = (MODE & RS_PF) != 0, FWD_B = (MODE & RS_NOB) == 0;
   constexpr bool OBSW = (MODE & RS_OBSW) != 0;
+  constexpr int STP = (MODE & RS_WT) ? ST_WT : ST_PLAIN;   // store_out policy of h (and of whatever else the role stores as a pure output)
   static_assert(!OBSW || (EXT != 0 && OBS && !STEP && !WH), "the observer role exists only inside the fused tick");
   constexpr bool NOJC = (MODE & RS_NOJC) != 0;
   static_assert(!NOJC || (EXT != 0 && STEP && !OBS && !WPF), "RS_NOJC: a step role next to a mass_jac role");
@@ -873,6 +877,7 @@ __global__ __launch_bounds__(BLOCK, WBC_RS_WAVES) void rnea_step_kernel(const De
 #undef STLX
 #undef STL
 #undef STV
+#undef WBC_ST
 #undef LDX
 #undef LDV
 #undef LDU

@@ -1,15 +1,10 @@
-// Fused control tick for SMALL batches: one kernel instead of {dyn_sweep -> qp_group16} while the batch fits one
-// workgroup per CU (N <= 4 096 = 256 CUs x 16 states; the bench default).  At that size both kernels are latency-bound
-// (one sweep wavefront and four QP wavefronts per CU, nothing to hide behind), and the two-kernel tick pays on top of
-// the arithmetic: two launches, the end-of-kernel drain of 3.5 kB/state of M/h/Jc stores -- which the QP never reads
-// -- before the QP may start, and a round trip of the 66-word step workspace through HBM.  Here a workgroup owns 16
-// consecutive states and hands the workspace over in LDS; M/h/Jc stores drain behind the QP.
-//
-// The front half is split by consumer into wavefront roles (below).  N = 4 096, observer off: 22.3 us per tick against
-// 32.5 us for the two-kernel tick (184 M vs 126 M control-steps/s); observer on (two more wavefronts): 21.2 us against
-// 34.3 us (193 M vs 120 M).  (A whole-sweep-then-QP fusion was measured before this one: -7 % / no gain.)
-// Larger batches keep the two-kernel tick: the sweep is HBM-bound there and wants all lanes of 8 waves per CU, which
-// the fused kernels' LDS (100 kB per workgroup in fp64) does not allow; measured slower from N = 8 192 on.
+// The one-launch control tick: the whole tick of a batch that fits one round of workgroups as ONE kernel instead of {dyn_sweep -> QP}.  A workgroup owns 16
+// consecutive states; its wavefronts are ROLES that hand the 66-word step workspace over in LDS (no launch boundary, no round trip of the workspace through
+// memory), and the M / h / Jc stores -- which no role reads back -- drain behind the QP.  At these sizes (the bench default: 4 096 fp64 states = 256 CUs x 16)
+// every stage is latency-bound: the kernel lasts as long as the dependent chain of its workgroup's hardest QP.
+// Which batches take it: the planner (wbc_api.cpp; the table of DESIGN.md 5); above it the pair tick below and the tile
+// tick (tile_tick.hip.hpp) take over, and large batches keep the two-launch tick, whose sweep is bandwidth-bound and wants every lane of eight wavefronts per CU.
+// History of the layout and of what was measured on the way: docs/DESIGN_R04.md, docs/DESIGN_R05.md, docs/DESIGN_HISTORY.md.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_types.hpp"
@@ -43,10 +38,9 @@ constexpr int FUSED_OBS_WAVES = 2;
 // rhat follows from the observer role (`oready`,
 // first needed for g = -A^T S b) and tau_partial + the own-leg Jacobian blocks when the force recursions are done
 // (`ready`, first needed in the torque map).  Observer off, N = 4 096: 25.5 -> 22.5 us per tick.
-// Observer off, M/h/Jc wanted: the rnea role is TWO wavefronts (a seventh wavefront; with the observer on the CU's eight slots
-// are taken).  Wave 4 runs the ONE merged force recursion RNEA(q, v, vdot_des) -- tau_partial, all the QP's torque map waits
-// for -- and wave 6 the bias-force recursion whose only consumer is the caller's h buffer.  One wavefront doing both chains
-// (round 2) kept the QP wavefronts waiting for tau_partial until +9.1 us.
+// WARM ticks, observer off, M/h/Jc wanted, fp64 (fused_split_h): the rnea role is TWO wavefronts (a seventh wavefront; with the observer on the CU's eight slots
+// are taken).  Wave 4 runs the ONE merged force recursion RNEA(q, v, vdot_des) -- tau_partial, all the QP's torque map waits for -- and wave 6 the bias-force
+// recursion whose only consumer is the caller's h buffer.  The COLD tick keeps both chains on wave 4: there the QP, not the rnea role, ends the tick.
 // 1 (default, round 5): the observer role stores r only after the QP wavefronts have read r_prev (QpSync::rp_ack); 0: the unordered read of round 4 (A/B)
 // (fp64 only: the fp32 tick fits two six-wavefront workgroups on a CU -- 147 VGPRs, 49 kB LDS -- and a seventh wavefront would end that)
 // WARM ticks are another matter: the block set-up ends the QP at about +5.5 us, so the tick ends with the rnea role and its torque map, and taking
@@ -57,6 +51,14 @@ constexpr int FUSED_OBS_WAVES = 2;
 template <class T, bool OBSERVER, bool MATS, bool WARM = false> constexpr bool fused_split_h() {
   return !OBSERVER && MATS && WARM && sizeof(T) == 8;
 }
+// Store policy of M, h, Jc, pf (device_types.hpp, store_out): the COLD fp64 tick that writes them stores them write-through, observer off and on.
+// 4 096 fp64 states: kernel 13.23 -> 12.15 us, 309 -> 340 M steps/s -- what the tick reaches when it writes no M, h, Jc at all;
+// observer on 314 -> 339 M (profiles/r07_store_policy_measure.log).  Warm ticks end with the rnea role, not the QP, and keep plain stores.  So does the pair tick
+// (fused_pair_kernel): two runs at 8 192 states gave 397 - 400 -> 412 M, but 6 144 states were not measured, and it takes both to turn it on there.
+// fp32 keeps plain stores: with other stores in the role bodies the compiler packs other pairs of fp32 multiplies (v_pk_mul_f32 in place of fused multiply-adds: 49 fewer
+// fmas in the fp32 tick), so M came out with other last bits than the warm tick, the two-launch tick and every earlier build give -- and those are compared bit for bit
+// (tests/test_gpu_warm.py).  fp64 has no packed arithmetic: its instruction mix, and its bits, are those of the plain-store build.
+template <class T, bool MATS, bool WARM> constexpr int fused_store() { return (MATS && !WARM && sizeof(T) == 8) ? ST_WT : ST_PLAIN; }
 template <class T, bool OBSERVER, bool MATS, bool WARM = false> constexpr int fused_threads() { return OBSERVER ? 384 + 64 * FUSED_OBS_WAVES : (fused_split_h<T, OBSERVER, MATS, WARM>() ? 448 : 384); }
 // WARM: the QP of every state starts from the active set in qa.aset_in (wbc_step_batch_warm: dependent ticks of a closed loop)
 template <class T, bool OBSERVER, bool MATS, bool WARM = false>
@@ -83,7 +85,7 @@ __global__ __launch_bounds__((fused_threads<T, OBSERVER, MATS, WARM>()), 1) void
   // barrier from inside their bodies (EXT = 2), so table staging and state loads share a memory round trip.
   if (wave == 4) {
     int* const gflag = &gready;
-    constexpr int RMODE = (MATS && !fused_split_h<T, OBSERVER, MATS, WARM>()) ? (RS_STEP | RS_H) : RS_STEP;
+    constexpr int RMODE = ((MATS && !fused_split_h<T, OBSERVER, MATS, WARM>()) ? (RS_STEP | RS_H) : RS_STEP) | (fused_store<T, MATS, WARM>() == ST_WT ? RS_WT : 0);
     auto geom_out = [=] __device__() {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
       if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(gflag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -95,7 +97,7 @@ __global__ __launch_bounds__((fused_threads<T, OBSERVER, MATS, WARM>()), 1) void
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");     // my LDS writes first (lgkmcnt only) ...
     if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(&ready, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // ... then the flag
   } else if (wave == 5) {
-    if constexpr (MATS) mass_jac_body<T, 64, 2, 16, (0)>(model, a, cst, zidx_s);   // (2: the role writes them LAST)
+    if constexpr (MATS) mass_jac_body<T, 64, 2, 16, (0), MjNoHook, fused_store<T, MATS, WARM>()>(model, a, cst, zidx_s);   // (2: the role writes them LAST)
     else __syncthreads();
     FSTAMP(9);
   } else if (fused_split_h<T, OBSERVER, MATS, WARM>() && wave == 6) {
@@ -132,7 +134,7 @@ __global__ __launch_bounds__((fused_threads<T, OBSERVER, MATS, WARM>()), 1) void
     if constexpr (MATS) {
       const int* const zs = zidx_s;
       const unsigned tq = threadIdx.x;
-      auto idle = [=] __device__() { if (!a.skip_consts) structural_consts_quarter<T>(model, a, zs, tq); };
+      auto idle = [=] __device__() { if (!a.skip_consts) structural_consts_quarter<T, fused_store<T, MATS, WARM>()>(model, a, zs, tq); };
       qp_body<T, true, OBSERVER, 16, false, 4, decltype(idle), false, WARM ? 1 : 0>(prm, qa, jmap, wsl, &sy, QpWho{0, false}, idle);
     } else
     qp_body<T, true, OBSERVER, 16, false, 4, QpNoIdle, false, WARM ? 1 : 0>(prm, qa, jmap, wsl, &sy);
