@@ -11,6 +11,7 @@
 // stubs -- they pin nothing about the real controller's topics or types, which are [UNVERIFIED]).
 #pragma once
 #include <array>
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -128,6 +129,27 @@ class QuadrupedWBC {
     Command c;
     check(wbc_compute_reference(solver_, q.data(), v.data(), row, t, c.w_des, c.vdot_des.data(), com_out), "wbc_compute_reference");
     return c;
+  }
+
+  // Joint torque limits (wbc_hip.h, "Joint torque limits behind a tick").  effortLimits(): the URDF's <limit effort> per joint in jointNames() order,
+  // HUGE_VAL where it gives none.  setTorqueLimits(): the limits the post-pass enforces (one value > 0 per joint; empty = back to the URDF's).
+  std::vector<double> effortLimits() const {
+    std::vector<double> lim(nj_);
+    check(wbc_model_effort_limits(model_, lim.data()), "wbc_model_effort_limits");
+    return lim;
+  }
+  void setTorqueLimits(const std::vector<double>& tau_max) {
+    if (tau_max.empty()) { check(wbc_solver_set_torque_limits(solver_, nullptr), "wbc_solver_set_torque_limits"); return; }
+    if ((int)tau_max.size() != nj_) throw std::invalid_argument("setTorqueLimits: one limit per joint");
+    wbc_torque_limits l;
+    l.struct_size = sizeof(l);
+    for (int j = 0; j < WBC_MAXV; ++j) l.tau_max[j] = j < nj_ ? tau_max[j] : HUGE_VAL;
+    check(wbc_solver_set_torque_limits(solver_, &l), "wbc_solver_set_torque_limits");
+  }
+  // wbc_step_limited_batch on this robot's solver (one state): in / out / obs hold DEVICE pointers as for wbc_step_batch, out.M, h, Jc included;
+  // limited (device, one int32) may be null.  Enqueues on `stream` and returns without synchronising.
+  void stepLimited(const wbc_batch_in& in, const wbc_batch_out& out, const wbc_observer_state* obs, int* limited, void* stream = nullptr) {
+    check(wbc_step_limited_batch(solver_, 1, &in, &out, obs, limited, stream), "wbc_step_limited_batch");
   }
 
   // Observer state (the only per-robot state carried across ticks): snapshot / restore / initialise.

@@ -89,6 +89,9 @@ int wbc_model_get_flat(const wbc_model* m, int* parent, double* Rt, double* rt, 
 const char* wbc_model_joint_name(const wbc_model* m, int j); /* NULL if out of range / unnamed */
 const char* wbc_model_foot_link(const wbc_model* m, int k);
 double wbc_model_total_mass(const wbc_model* m);
+/* <limit effort="..."> of each actuated joint: lim[nj], caller's joint order (wbc_model_joint_name); HUGE_VAL where the URDF gives none
+ * and for wbc_model_from_flat models */
+int wbc_model_effort_limits(const wbc_model* m, double* lim);
 
 void wbc_params_default(wbc_params* p, int dtype);
 
@@ -392,6 +395,38 @@ int wbc_score_batch(wbc_solver* s, size_t N, const void* q, const void* v, const
  * No solver: dtype (WBC_F64 / WBC_F32) names the scalar type; runs on the current device.  Bit-identical from run to run. */
 int wbc_rollout_select(int dtype, size_t n_groups, size_t group, const void* cost, double lambda, int* best, void* best_cost,
                        void* weights, void* stream);
+
+/* Joint torque limits behind a tick.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct changes; detect it by these symbols).
+ * wbc_step_batch itself never applies limits.  The post-pass works per state on the tick's own outputs: a state whose torques are all within
+ * |tau_j| <= tau_max[j] (compared exactly, no tolerance) is left untouched bit for bit; a state with a STANCE-leg joint beyond its limit gets its GRF QP
+ * solved again on chip with the rows |tau0_j - a_j^T f| <= tau_max[j] added (tau0 = tau + (Jc^T f)_joint rows, the force-free torque; a_j = column 6 + j of
+ * Jc; same objective, friction pyramid and normal-force box as the tick, wbc_params.qp_tol and max_iter, fp64 arithmetic for both scalar types), and f, tau,
+ * status, iters are rewritten from it.  limited [N] int32 says what happened:
+ *   0  within the limits: tau, f, status, iters untouched
+ *   1  re-solved: status = 0, iters = the limited QP's iterations, every stance-leg |tau_j| <= tau_max[j] + qp_tol
+ *   2  clamped: a SWING-leg joint was beyond its limit (no contact force can change it: tau_j = +-tau_max[j]; f and the stance legs follow 0 or 1), or
+ *      the limited QP ended in status 1 / 2 (the tick's f and status stay, every tau_j is clipped).  A clamped state's tau no longer realises vdot_des.
+ * Stream rules as for wbc_step_batch: two launches and a 4-byte memset on the caller's stream, no allocation, no synchronisation, hipGraph-capturable.
+ * The limits travel as a kernel argument: nothing is uploaded, and a captured graph keeps the limits it was captured with.  When every limit is
+ * HUGE_VAL nothing is launched.  N == 0 returns WBC_OK without looking at the buffers, as wbc_step_batch does.  The list of saturated states and its
+ * counter belong to the solver: post-passes of ONE solver must be ordered on one stream (or by events); two of them running at once on different
+ * streams race on that list.  A clipped torque is tau_max[j] rounded to the solver's scalar type.  Not part of the one-launch rollout kernels or of the wbc_multi_* entry points (a shard's caller runs the post-pass on the
+ * shard's solver and stream); velocity and position limits are not modelled. */
+typedef struct wbc_torque_limits {
+  size_t struct_size;        /* sizeof(wbc_torque_limits) of the caller's build */
+  double tau_max[WBC_MAXV];  /* > 0, caller's joint order; HUGE_VAL = none */
+} wbc_torque_limits;
+/* l == NULL: back to the model's effort limits (what a new solver starts with).  Not inside a stream capture. */
+int wbc_solver_set_torque_limits(wbc_solver* s, const wbc_torque_limits* l);
+/* the post-pass alone, behind ANY tick of the same N on the same stream (wbc_step_batch, wbc_step_batch_warm, a shard's tick): in / out / obs are that
+ * tick's; out->M, h, Jc are required (Jc is read); limited may be NULL */
+int wbc_limit_torques_batch(wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs,
+                            int* limited, void* stream);
+/* wbc_step_batch followed by wbc_limit_torques_batch; every argument check of both runs before anything is enqueued */
+int wbc_step_limited_batch(wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs,
+                           int* limited, void* stream);
+/* diagnostics (synchronises the device): how many states the last post-pass re-solved */
+int wbc_solver_limited_count(wbc_solver* s, int* resolved);
 
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and

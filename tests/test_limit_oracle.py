@@ -1,0 +1,145 @@
+"""CPU: joint torque limits -- the model's effort limits through the host ABI, the numpy reference of the post-pass (tests/limit_ref.py) against the
+conditions that define its result, the two constructed clamp cases, the exported symbols, and the resources of the new kernel unit."""
+import ctypes as C
+import functools
+import importlib.util
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import limit_ref
+from wbc_quadruped_dob_amd import synth
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+GAZEBO_URDF = os.path.join(ROOT, "tests", "golden", "gazebo_like_quadruped.urdf")
+# states re-solved out of 256 of make_batch(cfg, 256, m_total, rank=3), default params, observer off (measured with the oracle when the feature was specified)
+COUNTS = {(2, 60.0): 32, (3, 60.0): 47, (4, 60.0): 60, (2, 45.0): 78, (3, 45.0): 138, (4, 45.0): 126, (2, 8.0): 256, (3, 8.0): 256, (4, 8.0): 256}
+
+
+def test_effort_limits_from_the_urdf(hip_lib, gpu_model):
+    import wbc_quadruped_dob_amd as W
+    lim = gpu_model.effort_limits()
+    assert lim.shape == (12,) and np.all(lim == 60.0)
+    # the Gazebo-like fixture: roll and pitch joints carry <limit effort="55">, the continuous knees carry no <limit> at all
+    gz = W.Model.from_urdf(GAZEBO_URDF, foot_links=["fl_foot", "fr_foot", "rl_foot", "rr_foot"])
+    names = gz.flat()["joint_names"]
+    glim = gz.effort_limits()
+    for name, x in zip(names, glim):
+        assert x == (np.inf if name.endswith("_knee") else 55.0), (name, x)
+    assert sum(n.endswith("_knee") for n in names) == 4
+    assert np.all(np.isinf(W.Model.from_flat(gpu_model.flat()).effort_limits()))
+    assert hip_lib.wbc_model_effort_limits(None, glim.ctypes.data_as(C.c_void_p)) == 1   # WBC_E_INVALID
+    assert hip_lib.wbc_model_effort_limits(gpu_model._h, None) == 1
+
+
+@functools.lru_cache(maxsize=None)
+def _ref(cfg, lim, total_mass):
+    from oracle import oracle_py, urdf_model
+    import wbc_quadruped_dob_amd as W
+    orc = oracle_py.Oracle(urdf_model.load_urdf(W.SYNTHETIC_URDF))
+    P = synth.default_params()
+    B = synth.make_batch(cfg, 256, total_mass, rank=3)
+    return P, B, limit_ref.step_limited(orc, P, B, lim, want_qp=True)
+
+
+@pytest.mark.parametrize("cfg", [2, 3, 4])
+@pytest.mark.parametrize("lim", [60.0, 45.0, 8.0])
+def test_reference_is_sound(gpu_model, flat_model, cfg, lim):
+    """Every re-solved state satisfies the KKT conditions of the QP with the torque rows (residuals in numpy, the gate of tests/test_gpu_kkt.py's fp64
+    case: 1e-7 of the state's force scale for stationarity and complementarity, 1e-6 N for violated rows), its stance torques are within the limit, and
+    as many states are re-solved as the oracle measured."""
+    P, B, o = _ref(cfg, lim, gpu_model.total_mass)
+    legs = limit_ref.leg_joints(flat_model)
+    one = np.flatnonzero(o["limited"] == 1)
+    assert len(one) == COUNTS[(cfg, lim)] and not (o["limited"] == 2).any()
+    assert np.all(o["status"][one] == 0)
+    assert np.all(np.abs(o["tick"]["tau"][o["limited"] == 0]) <= lim)
+    worst = 0.0
+    for s in one:
+        H, g, Cm, d, x, lam = o["qp"][s]
+        scale = max(1.0, np.abs(x).max())
+        stat = np.abs(H @ x + g - Cm.T @ lam).max() / scale
+        slack = Cm @ x - d
+        assert stat < 1e-7 and slack.min() > -1e-6 and lam.min() >= 0 and np.abs(lam * slack).max() / scale < 1e-7, (s, stat, slack.min())
+        stance = [j for k in range(4) if (B["mask"][s] >> k) & 1 for j in legs[k]]
+        worst = max(worst, (np.abs(o["tau"][s, stance]) - lim).max())
+        # the rewritten torque is the torque map of the new forces: tau = tau_tick + (Jc^T (f_tick - f_new))_joint rows
+        J = o["dyn"]["Jc"][s].reshape(12, 18)
+        assert np.abs(o["tau"][s] - (o["tick"]["tau"][s] + J[:, 6:].T @ (o["tick"]["f"][s] - o["f"][s]))).max() < 1e-9
+    assert worst <= P["qp_tol"], worst
+
+
+def test_constructed_clamp_cases_exist_in_the_reference(gpu_model, oracle, flat_model):
+    P = synth.default_params()
+    B = limit_ref.swing_case(gpu_model.total_mass)
+    o = limit_ref.step_limited(oracle, P, B, 45.0)
+    legs = limit_ref.leg_joints(flat_model)
+    two = np.flatnonzero(o["limited"] == 2)
+    assert len(two) >= 8
+    for s in two:
+        swing = [j for k in range(4) if not (B["mask"][s] >> k) & 1 for j in legs[k]]
+        over = np.abs(o["tick"]["tau"][s, swing]) > 45.0
+        assert over.any() and np.all(np.abs(o["tau"][s, swing])[over] == 45.0)
+        assert np.array_equal(o["tau"][s, swing][~over], o["tick"]["tau"][s, swing][~over])
+    assert np.all(o["qp_status"][two] <= 0)   # (none of these is the other clamp case)
+    # no admissible force meets 0.05 N m while every stance foot must push with at least 20 N
+    P2 = synth.default_params(); P2["fn_min"] = 20.0
+    B2 = synth.make_batch(2, 64, gpu_model.total_mass, rank=3)
+    o2 = limit_ref.step_limited(oracle, P2, B2, 0.05)
+    assert np.all(o2["qp_status"] == 2) and np.all(o2["limited"] == 2)
+    assert np.array_equal(o2["f"], o2["tick"]["f"]) and np.array_equal(o2["status"], o2["tick"]["status"])
+    assert np.abs(o2["tau"]).max() == 0.05
+
+
+def test_symbols_are_exported_and_the_abi_is_still_10(hip_lib):
+    for name in ("wbc_model_effort_limits", "wbc_solver_set_torque_limits", "wbc_limit_torques_batch", "wbc_step_limited_batch", "wbc_solver_limited_count"):
+        assert hasattr(hip_lib, name), name
+    assert hip_lib.wbc_abi_version() == 10
+    # argument errors that need no device
+    assert hip_lib.wbc_solver_set_torque_limits(None, None) == 1
+    assert hip_lib.wbc_limit_torques_batch(None, 1, None, None, None, None, None) == 1
+    assert hip_lib.wbc_step_limited_batch(None, 1, None, None, None, None, None) == 1
+    assert hip_lib.wbc_solver_limited_count(None, None) == 1
+
+
+def test_a_library_without_the_limit_symbols_loads_and_only_the_limit_calls_refuse_it(hip_lib, gpu_model, monkeypatch):
+    """An ABI-10 build from before the post-pass (what tools/limit_profile.py's `tick` phase runs against through WBC_LIB): everything else works."""
+    import wbc_quadruped_dob_amd as W
+    new = ("wbc_model_effort_limits", "wbc_solver_set_torque_limits", "wbc_limit_torques_batch", "wbc_step_limited_batch", "wbc_solver_limited_count")
+
+    class Older:
+        def __getattr__(self, name):
+            if name in new:
+                raise AttributeError(name)
+            return getattr(hip_lib, name)
+
+    monkeypatch.setattr(W, "_lib", Older())
+    assert gpu_model.total_mass > 0 and len(gpu_model.flat()["joint_names"]) == 12
+    with pytest.raises(RuntimeError, match="lacks the torque-limit entry points"):
+        gpu_model.effort_limits()
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.parametrize("scalar", ["double", "float"])
+def test_limit_unit_compiles_and_the_scan_uses_no_scratch(tmp_path, scalar):
+    """k_limit.hip compiles for gfx950; limit_scan_kernel (a pure streaming pass) touches no scratch, and limit_qp_kernel keeps the 128 registers its
+    grid formula (launch.hpp, limit_qp_grid: four wavefronts per SIMD) counts on -- numbers read from the unit's metadata as tools/unit_resources.py does."""
+    spec = importlib.util.spec_from_file_location("spill_lint", os.path.join(ROOT, "tools", "spill_lint.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    out = str(tmp_path / "k_limit.s")
+    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-DWBC_SCALAR=" + scalar, "-S", "--cuda-device-only", "-w", "-o", out,
+                           "k_limit.hip"], cwd=os.path.join(ROOT, "wbc_quadruped_dob_amd", "csrc"))
+    res = mod.resources(out)
+    scan = {k: v for k, v in res.items() if re.search(r"limit_scan_kernelI[df]", k)}
+    qp = {k: v for k, v in res.items() if re.search(r"limit_qp_kernelI[df]", k)}
+    assert len(scan) == 1 and len(qp) == 1
+    for k, v in scan.items():
+        assert v["scratch"] == 0, (k, v)
+    for k, v in qp.items():
+        assert v["scratch"] == 0 and v["vgpr"] + v["agpr"] <= 128, (k, v)

@@ -241,6 +241,14 @@ def lib():
         L.wbc_rollout_scored_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 9
         L.wbc_score_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
         L.wbc_rollout_select.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # joint torque limits: additive to ABI 10 too, detected by the symbols.  An older build of the same ABI still loads (every other call works
+        # on it); the limit calls themselves refuse it (_limit_lib)
+        if hasattr(L, "wbc_step_limited_batch"):
+            L.wbc_model_effort_limits.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_solver_set_torque_limits.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_limit_torques_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
+            L.wbc_step_limited_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
+            L.wbc_solver_limited_count.argtypes = [C.c_void_p, C.c_void_p]
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -260,6 +268,14 @@ def lib():
         L.wbc_multi_probe_issue.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
+
+
+def _limit_lib():
+    """lib(), for the torque-limit calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_step_limited_batch"):
+        raise RuntimeError("%s lacks the torque-limit entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
 
 
 def _check(code, where):
@@ -307,6 +323,11 @@ class ScoreParams(C.Structure):
             else:
                 raise KeyError("ScoreParams has no field %r" % k)
         return p
+
+
+class TorqueLimits(C.Structure):
+    """wbc_torque_limits: tau_max > 0 per joint in the caller's joint order, inf = no limit."""
+    _fields_ = [("struct_size", C.c_size_t), ("tau_max", C.c_double * WBC_MAXV)]
 
 
 class RolloutScore(C.Structure):
@@ -400,6 +421,12 @@ class Model:
     @property
     def total_mass(self):
         return lib().wbc_model_total_mass(self._h)
+
+    def effort_limits(self):
+        """<limit effort> of each actuated joint (float64 [nj], caller's joint order); inf where the URDF gives none and for from_flat models."""
+        lim = np.zeros(self.nj)
+        _check(_limit_lib().wbc_model_effort_limits(self._h, lim.ctypes.data_as(C.c_void_p)), "wbc_model_effort_limits")
+        return lim
 
     def __del__(self):
         try:
@@ -523,6 +550,53 @@ class Solver:
         else:
             _check(lib().wbc_step_batch(self._h, N, C.byref(bi), C.byref(bo), C.byref(ob), self._stream()), "wbc_step_batch")
         return out
+
+    def set_torque_limits(self, tau_max=None):
+        """The limits the torque-limit post-pass enforces: a scalar or [nj] array (> 0, inf = none); None = the model's effort limits.
+        Not inside a stream capture (a captured graph keeps the limits it was captured with)."""
+        if tau_max is None:
+            _check(_limit_lib().wbc_solver_set_torque_limits(self._h, None), "wbc_solver_set_torque_limits")
+            return
+        t = TorqueLimits()
+        t.struct_size = C.sizeof(TorqueLimits)
+        lim = np.broadcast_to(np.asarray(tau_max, dtype=np.float64), (self.model.nj,))
+        for j in range(WBC_MAXV):
+            t.tau_max[j] = float(lim[j]) if j < self.model.nj else float("inf")
+        _check(_limit_lib().wbc_solver_set_torque_limits(self._h, C.byref(t)), "wbc_solver_set_torque_limits")
+
+    def limit_torques(self, w_des, normals, mu, mask, out, obs_r=None, limited=None):
+        """wbc_limit_torques_batch: the post-pass alone, behind any tick of the same batch on the current stream.  out = that tick's dict (tau, f,
+        status[, iters] are rewritten in place; M, h, Jc required), obs_r = the observer state the tick left (observer on).  Returns out with
+        out["limited"] (int32 [N]: 0 within limits, 1 re-solved, 2 clamped)."""
+        torch = self.torch
+        m = self.model
+        N = out["tau"].shape[1]
+        if limited is None:
+            limited = out.get("limited")
+        if limited is None:
+            limited = torch.empty(N, dtype=torch.int32, device=self.device)
+        out["limited"] = limited
+        bi, bo, ob = self._batch(N, None, None, w_des, None, normals, mu, mask, out, None, obs_r)
+        _check(_limit_lib().wbc_limit_torques_batch(self._h, N, C.byref(bi), C.byref(bo), C.byref(ob), self._ptr(limited, 1, N, torch.int32),
+                                             self._stream()), "wbc_limit_torques_batch")
+        return out
+
+    def step_limited(self, q, v, w_des, vdot_des, normals, mu, mask, tau_prev=None, f_prev=None, obs_integ=None, obs_r=None, out=None):
+        """wbc_step_limited_batch: step(want_mats=True) followed by the torque-limit post-pass.  Returns step()'s dict plus out["limited"]."""
+        torch = self.torch
+        out, (N, bi, bo, ob, keep, _) = self.step(q, v, w_des, vdot_des, normals, mu, mask, tau_prev, f_prev, obs_integ, obs_r, out=out,
+                                                  want_mats=True, _prepared=True)
+        if "limited" not in out:
+            out["limited"] = torch.empty(N, dtype=torch.int32, device=self.device)
+        _check(_limit_lib().wbc_step_limited_batch(self._h, N, C.byref(bi), C.byref(bo), C.byref(ob), self._ptr(out["limited"], 1, N, torch.int32),
+                                            self._stream()), "wbc_step_limited_batch")
+        return out
+
+    def limited_count(self):
+        """How many states the last post-pass re-solved (synchronises the device)."""
+        n = C.c_int(0)
+        _check(_limit_lib().wbc_solver_limited_count(self._h, C.byref(n)), "wbc_solver_limited_count")
+        return n.value
 
     def prepare_step(self, *args, **kw):
         """Same arguments as step(); validates them and builds the C argument structs ONCE.  Returns (tick, out):

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include "device_types.hpp"
 #include "qp_general_args.hpp"
+#include "limit_args.hpp"
 
 namespace wbc {
 
@@ -102,6 +103,23 @@ template <class T> hipError_t k_score_tick(const LaunchCtx& L, const ScoreArgs<T
 template <class T> hipError_t k_rollout_select(hipStream_t st, size_t n_groups, size_t group, const T* cost, T lambda, int* best, T* best_cost, T* weights);
 // qp_general_kernel<T>: dense QPs of run-time size (n <= 36 variables, m <= 64 rows, the first meq of them equalities), one per wavefront
 template <class T> hipError_t k_qp_general(const LaunchCtx& L, const QpGeneralArgs<T>& a);
+// the torque-limit post-pass behind a tick (limit.hip.hpp): limit_scan_kernel<T> lists the states with a stance-leg torque beyond its limit and clips
+// swing-leg torques; limit_qp_kernel<T> re-solves the listed states' GRF QPs with the limits as rows on `workgroups` workgroups (limit_qp_grid: one
+// resident round for a device of that many compute units)
+template <class T> hipError_t k_limit_scan(const LaunchCtx& L, const LimitArgs<T>& a);
+template <class T> hipError_t k_limit_qp(const LaunchCtx& L, const LimitArgs<T>& a, int workgroups);
+// One resident round of wavefronts, from the kernel's LDS footprint.  A wavefront's slice holds the limited QP at its largest (LIMIT_QP_N = 12 variables,
+// LIMIT_QP_M = 48 rows) in fp64 for both scalar types: qpg_lds_scalars(12, 48) = 1076 doubles = 8608 bytes; a workgroup of LIMIT_QP_WPB = 4 wavefronts takes
+// 34 432 bytes, so floor(163 840 / 34 432) = 4 workgroups = 16 wavefronts share a compute unit's 160 KB (at most 128 registers each, four per SIMD):
+//     grid = compute units x floor(LDS per compute unit / (LIMIT_QP_WPB x 8608)) workgroups  =  256 x 4 = 1024 workgroups = 4096 wavefronts on MI355X.
+// The list is walked with a grid stride, so a larger list takes further trips of the same wavefronts and a wrong guess costs time, never correctness.
+// The 160 KB are specific to gfx950 (CDNA4), the only target this library is built for: a constant, not read from the device properties.
+constexpr size_t GFX950_LDS_PER_CU = 160 * 1024;
+inline int limit_qp_grid(int compute_units) {
+  const size_t wg_bytes = (size_t)LIMIT_QP_WPB * qpg_lds_scalars(LIMIT_QP_N, LIMIT_QP_M) * sizeof(double);
+  const size_t per_cu = GFX950_LDS_PER_CU / wg_bytes;
+  return compute_units * (int)(per_cu < 1 ? 1 : per_cu);
+}
 // one thread: *ptr = value, system scope (the completion ticket of the flag-polled single-robot tick)
 hipError_t k_flag(hipStream_t st, unsigned* ptr, unsigned value);
 // the peer gather of wbc_multi_*: ONE launch copies `bytes` bytes at src to each of the nd <= 64 destinations (this device's or peer-mapped memory)

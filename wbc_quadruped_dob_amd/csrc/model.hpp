@@ -19,6 +19,7 @@ struct FlatModel {
   std::vector<double> foot_off;  // [nf*3]
   double gravity[3] = {0.0, 0.0, -9.81};
   std::vector<std::string> joint_names;  // [nb-1]
+  std::vector<double> effort_limit;      // [nb-1] <limit effort> of each actuated joint, HUGE_VAL = none (always so for wbc_model_from_flat models)
   std::vector<std::string> foot_links;   // [nf]
   std::vector<std::string> body_names;   // [nb]
   int nf() const { return (int)foot_body.size(); }

@@ -102,37 +102,32 @@ template <class T> __device__ __forceinline__ T qpg_dot(const T* a, int sa, cons
   return (s0 + s1) + (s2 + s3);
 }
 
+// The Goldfarb-Idnani iteration itself on a problem that already sits in the wavefront's LDS slice: H in the R area (lower triangle read), C in Cm, lam zeroed,
+// g_i / d_i in the registers of lane i.  Shared by qp_general_kernel (problems from memory) and limit_qp_kernel (limit.hip.hpp: problems built on chip).
+// On return x_out = x_i of lane i < n (also in L.xs), L.lam holds the multipliers, status_out / iter_out as the kernel reports them.
+template <class T> struct QpgLds { T *J, *R, *Cm, *xs, *nps, *dds, *zs, *ccs, *sss, *rdg, *lam; };
+template <class T> __device__ __forceinline__ QpgLds<T> qpg_carve(T* S, int n, int m, int ld) {
+  QpgLds<T> L;
+  L.J = S;                        // n x ld
+  L.R = L.J + n * ld;             // n x ld   (holds H, then L, until the first constraint is added)
+  L.Cm = L.R + n * ld;            // m x ld
+  L.xs = L.Cm + m * ld;           // n+1 each:
+  L.nps = L.xs + (n + 1);
+  L.dds = L.nps + (n + 1);
+  L.zs = L.dds + (n + 1);
+  L.ccs = L.zs + (n + 1);
+  L.sss = L.ccs + (n + 1);
+  L.rdg = L.sss + (n + 1);        // reciprocals of the diagonal of R
+  L.lam = L.rdg + (n + 1);        // m+1
+  return L;
+}
 template <class T>
-__global__ __launch_bounds__(256) void qp_general_kernel(QpGeneralArgs<T> a, int lds_per_qp) {
-  extern __shared__ __align__(16) unsigned char qpg_lds_raw[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-  const size_t qp = (size_t)blockIdx.x * wpb + wave;
-  if (qp >= a.N) return;   // (whole wavefronts leave: no workgroup barrier anywhere below)
-  const int n = a.n, m = a.m, meq = a.meq, ld = qpg_ld(n);
-  T* const S = (T*)qpg_lds_raw + (size_t)wave * lds_per_qp;
-  T* const J = S;                      // n x ld
-  T* const R = J + n * ld;             // n x ld   (holds H, then L, until the first constraint is added)
-  T* const Cm = R + n * ld;            // m x ld
-  T* const xs = Cm + m * ld;           // n+1 each:
-  T* const nps = xs + (n + 1);
-  T* const dds = nps + (n + 1);
-  T* const zs = dds + (n + 1);
-  T* const ccs = zs + (n + 1);
-  T* const sss = ccs + (n + 1);
-  T* const rdg = sss + (n + 1);        // reciprocals of the diagonal of R
-  T* const lam = rdg + (n + 1);        // m+1
+__device__ __forceinline__ void qpg_solve(const QpgLds<T>& L, int lane, int n, int m, int meq, int ld, T g_i, T d_i, T tol, int max_iter,
+                                          T& x_out, int& status_out, int& iter_out) {
+  T* const J = L.J; T* const R = L.R; T* const Cm = L.Cm; T* const xs = L.xs; T* const nps = L.nps; T* const dds = L.dds; T* const zs = L.zs;
+  T* const ccs = L.ccs; T* const sss = L.sss; T* const rdg = L.rdg; T* const lam = L.lam;
   const T INF = QpgLim<T>::big, eps = QpgLim<T>::eps;
-
-  // ---- inputs (coalesced: consecutive lanes, consecutive elements of the problem's own block)
-  const T* Hq = a.H + qp * (size_t)n * n;
-  for (int e = lane; e < n * n; e += 64) { const int i = e / n, j = e - i * n; R[i * ld + j] = Hq[e]; }
-  const T* Cq = a.C + qp * (size_t)m * n;
-  for (int e = lane; e < m * n; e += 64) { const int i = e / n, j = e - i * n; Cm[i * ld + j] = Cq[e]; }
-  const T g_i = lane < n ? a.g[qp * n + lane] : (T)0;
-  const T d_i = lane < m ? a.d[qp * m + lane] : (T)0;
-  if (lane <= m) lam[lane] = 0;
   int status = 0, iter = 0;
-  QPG_WSYNC();
 
   // ---- Cholesky H = L L^T in place (lower triangle of the R area), column by column; lane i owns row i
   bool notpd = false;
@@ -148,12 +143,7 @@ __global__ __launch_bounds__(256) void qp_general_kernel(QpGeneralArgs<T> a, int
     if (lane >= j && lane < n) R[lane * ld + j] = (lane == j) ? ljj : s / ljj;
     QPG_WSYNC();
   }
-  if (notpd) {   // not positive definite: nothing to solve
-    if (lane < n) a.x[qp * n + lane] = 0;
-    if (a.lambda && lane < m) a.lambda[qp * m + lane] = 0;
-    if (lane == 0) { a.status[qp] = 3; if (a.iters) a.iters[qp] = 0; }
-    return;
-  }
+  if (notpd) { x_out = 0; status_out = 3; iter_out = 0; return; }   // not positive definite: nothing to solve (lam stays zero)
   // ---- J = L^-T (upper triangular): lane c solves L^T J[:, c] = e_c from the bottom up
   if (lane < n) {
     const int c = lane;
@@ -194,7 +184,7 @@ __global__ __launch_bounds__(256) void qp_general_kernel(QpGeneralArgs<T> a, int
       const T s = qpg_rl_dyn(s_i, next_eq);
       ip = next_eq++; is_eq = true; sign = s > 0 ? (T)-1 : (T)1; sip = -fabs(s);
     } else {
-      T v = (lane >= meq && lane < m && !active_i && s_i < -a.tol) ? s_i : INF;
+      T v = (lane >= meq && lane < m && !active_i && s_i < -tol) ? s_i : INF;
       int id = lane;
       qpg_wave_argmin(v, id);
       if (!(v < INF)) break;
@@ -206,7 +196,7 @@ __global__ __launch_bounds__(256) void qp_general_kernel(QpGeneralArgs<T> a, int
     QPG_WSYNC();
     // step 2
     for (;;) {
-      if (++iter > a.max_iter) { status = 1; finished = true; break; }
+      if (++iter > max_iter) { status = 1; finished = true; break; }
       T dd_i = 0;
       if (lane < n) dd_i = qpg_dot(J + lane, ld, nps, 1, 0, n);
       if (lane < n) dds[lane] = dd_i;
@@ -234,7 +224,7 @@ __global__ __launch_bounds__(256) void qp_general_kernel(QpGeneralArgs<T> a, int
       const bool no1 = !(t1 < INF), no2 = !(t2 < INF);
       bool do_drop = false;
       if (no1 && no2) {
-        if (is_eq && -sip <= a.tol) {   // dependent equality row that already holds: leave it out of the factors
+        if (is_eq && -sip <= tol) {   // dependent equality row that already holds: leave it out of the factors
           if (lane == iq) { A_s = -1; u_s = 0; sg_s = 1; }
           if (lane == ip) active_i = true;
           break;
@@ -328,9 +318,35 @@ __global__ __launch_bounds__(256) void qp_general_kernel(QpGeneralArgs<T> a, int
     }
   }
 
-  // ---- outputs
   if (lane < iq && A_s >= 0) lam[A_s] = sg_s * u_s;
   QPG_WSYNC();
+  x_out = x_i; status_out = status; iter_out = iter;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void qp_general_kernel(QpGeneralArgs<T> a, int lds_per_qp) {
+  extern __shared__ __align__(16) unsigned char qpg_lds_raw[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+  const size_t qp = (size_t)blockIdx.x * wpb + wave;
+  if (qp >= a.N) return;   // (whole wavefronts leave: no workgroup barrier anywhere below)
+  const int n = a.n, m = a.m, meq = a.meq, ld = qpg_ld(n);
+  const QpgLds<T> L = qpg_carve((T*)qpg_lds_raw + (size_t)wave * lds_per_qp, n, m, ld);
+  T* const R = L.R; T* const Cm = L.Cm; T* const lam = L.lam;
+
+  // ---- inputs (coalesced: consecutive lanes, consecutive elements of the problem's own block)
+  const T* Hq = a.H + qp * (size_t)n * n;
+  for (int e = lane; e < n * n; e += 64) { const int i = e / n, j = e - i * n; R[i * ld + j] = Hq[e]; }
+  const T* Cq = a.C + qp * (size_t)m * n;
+  for (int e = lane; e < m * n; e += 64) { const int i = e / n, j = e - i * n; Cm[i * ld + j] = Cq[e]; }
+  const T g_i = lane < n ? a.g[qp * n + lane] : (T)0;
+  const T d_i = lane < m ? a.d[qp * m + lane] : (T)0;
+  if (lane <= m) lam[lane] = 0;
+  QPG_WSYNC();
+
+  T x_i; int status, iter;
+  qpg_solve(L, lane, n, m, meq, ld, g_i, d_i, a.tol, a.max_iter, x_i, status, iter);
+
+  // ---- outputs
   if (lane < n) a.x[qp * n + lane] = x_i;
   if (a.lambda && lane < m) a.lambda[qp * m + lane] = lam[lane];
   if (lane == 0) { a.status[qp] = status; if (a.iters) a.iters[qp] = iter; }

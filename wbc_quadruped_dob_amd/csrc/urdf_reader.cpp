@@ -178,6 +178,7 @@ struct Joint {
   std::string name, type, parent, child;
   Mat3 R;
   double r[3], axis[3];
+  double effort = HUGE_VAL;   // <limit effort="...">, HUGE_VAL when the joint carries none
 };
 
 struct Body {
@@ -263,6 +264,13 @@ int load_urdf(const std::string& path, const std::vector<std::string>& foot_link
       double nrm = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
       if (j.type != "fixed" && nrm == 0.0) { err = "zero axis in joint " + j.name; return WBC_E_PARSE; }
       for (int q = 0; q < 3; ++q) j.axis[q] = nrm > 0 ? ax[q] / nrm : ax[q];
+      if (const Elem* l = k->child("limit")) {
+        const std::string e = l->get("effort", "");
+        double ev;
+        // (a file that loaded before effort limits were read still loads: anything but a positive number counts as "none";
+        //  effort="0" is what exporters write for "not set")
+        if (!e.empty() && parse_vec(e, 1, &ev) && ev > 0 && std::isfinite(ev)) j.effort = ev;
+      }
       joints.push_back(j);
     }
   }
@@ -280,6 +288,7 @@ int load_urdf(const std::string& path, const std::vector<std::string>& foot_link
   std::vector<Body> bodies;
   std::map<std::string, Frame> frames;
   std::vector<std::string> jnames;
+  std::vector<double> jeffort;
   Body base;
   base.parent = -1; base.Rt = ident3();
   for (int q = 0; q < 3; ++q) base.rt[q] = base.axis[q] = 0;
@@ -288,7 +297,7 @@ int load_urdf(const std::string& path, const std::vector<std::string>& foot_link
 
   // depth-first, children in document order (explicit stack would reorder; use recursion)
   struct Rec {
-    std::vector<Body>& bodies; std::map<std::string, Frame>& frames; std::vector<std::string>& jnames;
+    std::vector<Body>& bodies; std::map<std::string, Frame>& frames; std::vector<std::string>& jnames; std::vector<double>& jeffort;
     const std::map<std::string, Inertia>& links; const std::vector<Joint>& joints; int depth = 0; bool bad = false;
     void visit(const std::string& link, int body, const Mat3& R, const double* r) {
       if (++depth > 256) { bad = true; return; }
@@ -314,13 +323,14 @@ int load_urdf(const std::string& path, const std::vector<std::string>& foot_link
           b.name = j.child;
           bodies.push_back(b);
           jnames.push_back(j.name);
+          jeffort.push_back(j.effort);
           double z[3] = {0, 0, 0};
           visit(j.child, (int)bodies.size() - 1, ident3(), z);
         }
       }
       --depth;
     }
-  } rec{bodies, frames, jnames, links, joints};
+  } rec{bodies, frames, jnames, jeffort, links, joints};
   double z3[3] = {0, 0, 0};
   rec.visit(rootlink, 0, ident3(), z3);
   if (rec.bad) { err = "kinematic loop or tree deeper than 256"; return WBC_E_PARSE; }
@@ -355,6 +365,7 @@ int load_urdf(const std::string& path, const std::vector<std::string>& foot_link
     for (int q = 0; q < 3; ++q) out.foot_off.push_back(frames[n].r[q]);
   }
   out.joint_names = jnames;
+  out.effort_limit = jeffort;
   out.foot_links = feet;
   return WBC_OK;
 }

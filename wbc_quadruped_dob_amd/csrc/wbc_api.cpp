@@ -90,6 +90,12 @@ struct wbc_solver {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   void* d_ref = nullptr;     // DevRefParams<T>, set by wbc_solver_set_ref_params
   wbc_score_params score;    // the weights of the scored rollouts (wbc_solver_set_score_params; kernel arguments by value), defaults at creation
+  // torque-limit post-pass (wbc_limit_torques_batch): the limits travel as a kernel argument like the score weights
+  double tau_max[WBC_MAXV];  // caller's joint order, HUGE_VAL = none; the model's effort limits at creation
+  double model_effort[WBC_MAXV];
+  int* d_limit = nullptr;    // LIMIT_LIST_HEAD + max_batch ints: [0] = how many states the scan listed, then their indices
+  int limit_grid = 0;        // workgroups of limit_qp_kernel: one resident round on this device (limit_qp_grid)
+  bool limit_skipped = true; // the last post-pass launched nothing (every limit +inf)
   // N=1 convenience buffers
   void* d_one = nullptr;
   void* h_one = nullptr;       // pinned host image of d_one: the single-robot calls move it with ONE copy each way
@@ -203,6 +209,13 @@ extern "C" double wbc_model_total_mass(const wbc_model* m) {
   double s = 0;
   for (double x : m->fm.mass) s += x;
   return s;
+}
+
+extern "C" int wbc_model_effort_limits(const wbc_model* m, double* lim) {
+  if (!m || !lim) return fail(WBC_E_INVALID, "null argument");
+  const int nj = m->fm.nj();
+  for (int j = 0; j < nj; ++j) lim[j] = j < (int)m->fm.effort_limit.size() ? m->fm.effort_limit[j] : HUGE_VAL;
+  return WBC_OK;
 }
 
 extern "C" void wbc_params_default(wbc_params* p, int dtype) {
@@ -652,6 +665,9 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   if (!s) return fail(WBC_E_INVALID, "out of memory");
   s->dtype = dtype; s->device = device; s->max_batch = max_batch; s->params = *p; s->opt = o;
   wbc_score_params_default(&s->score);
+  for (int j = 0; j < WBC_MAXV; ++j) s->model_effort[j] = (j < m->fm.nj() && j < (int)m->fm.effort_limit.size()) ? m->fm.effort_limit[j] : HUGE_VAL;
+  std::memcpy(s->tau_max, s->model_effort, sizeof(s->tau_max));
+  s->limit_grid = limit_qp_grid(prop.multiProcessorCount);
   s->rz = resolve_options(dtype, o);
   std::memcpy(s->leg_body, leg_body, sizeof(leg_body));
   for (int l = 0; l < 4; ++l) for (int k = 0; k < 3; ++k) s->jmap.j[3 * l + k] = leg_body[l][k] - 1;
@@ -675,6 +691,8 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   if (e == hipSuccess) e = hipMemset(s->d_todo, 0, 4 * sizeof(int));
   if (e == hipSuccess) e = hipMalloc((void**)&s->d_aset, max_batch * sizeof(int));
   if (e == hipSuccess) e = hipMemset(s->d_aset, 0, max_batch * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&s->d_limit, (max_batch + LIMIT_LIST_HEAD) * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(s->d_limit, 0, LIMIT_LIST_HEAD * sizeof(int));
   // N = 1 image: q19 v18 w6 a18 n12 mu4 tp12 fp12 integ18 r18 tau12 f12 (scalars; 161 of ONE_TICK_SCALARS), a scratch region for
   // the start-up / planner helpers (wbc_observer_init, wbc_compute_reference: they must not touch what a caller keeps in the
   // image between ticks, wbc_one_map), then the ints mask | status | iters | completion ticket
@@ -711,6 +729,7 @@ extern "C" void wbc_solver_destroy(wbc_solver* s) {
   if (s->d_ws) (void)hipFree(s->d_ws);
   if (s->d_todo) (void)hipFree(s->d_todo);
   if (s->d_aset) (void)hipFree(s->d_aset);
+  if (s->d_limit) (void)hipFree(s->d_limit);
   if (s->d_one) (void)hipFree(s->d_one);
   if (s->h_one) (void)hipHostFree(s->h_one);
   if (s->d_ref) (void)hipFree(s->d_ref);
@@ -1059,6 +1078,88 @@ extern "C" int wbc_step_batch_warm(wbc_solver* s, size_t N, const wbc_batch_in* 
   hipStream_t st = (hipStream_t)stream;
   return s->dtype == WBC_F64 ? step_impl<double>(s, N, in, out, obs, st, true, active_in, active_out)
                              : step_impl<float>(s, N, in, out, obs, st, true, active_in, active_out);
+}
+
+// ---- joint torque limits behind a tick (limit.hip.hpp)
+extern "C" int wbc_solver_set_torque_limits(wbc_solver* s, const wbc_torque_limits* l) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (!l) { std::memcpy(s->tau_max, s->model_effort, sizeof(s->tau_max)); return WBC_OK; }
+  if (l->struct_size < sizeof(wbc_torque_limits)) return fail(WBC_E_INVALID, "wbc_torque_limits: struct_size too small");
+  for (int j = 0; j < 12; ++j)
+    if (!(l->tau_max[j] > 0)) return fail(WBC_E_INVALID, "wbc_torque_limits: tau_max must be > 0 (HUGE_VAL = no limit)");
+  for (int j = 0; j < WBC_MAXV; ++j) s->tau_max[j] = j < 12 ? l->tau_max[j] : HUGE_VAL;
+  return WBC_OK;
+}
+
+// the post-pass's own argument checks (no HIP call)
+static int check_limit_args(const wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs) {
+  if (!s || !in || !out) return fail(WBC_E_INVALID, "null argument");
+  if (N == 0) return WBC_OK;   // (as check_step_args: an empty batch needs no buffers)
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  if (!in->w_des || !in->normals || !in->mu || !in->mask) return fail(WBC_E_INVALID, "null input buffer");
+  if (!out->tau || !out->f || !out->status) return fail(WBC_E_INVALID, "null output buffer");
+  if (!out->M || !out->h || !out->Jc) return fail(WBC_E_INVALID, "torque limits: out->M, h, Jc are required (the post-pass reads Jc)");
+  if (s->params.observer_order > 0 && (!obs || !obs->r)) return fail(WBC_E_INVALID, "observer on: observer state buffers required");
+  return WBC_OK;
+}
+
+template <class T>
+static int limit_impl(wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs, int* limited, hipStream_t st) {
+  bool any = false;
+  for (int j = 0; j < 12; ++j) any = any || s->tau_max[j] < HUGE_VAL;
+  s->limit_skipped = !any;
+  if (!any) {   // nothing can saturate: no launch, every state is outcome 0
+    if (limited) HIP_TRY(hipMemsetAsync(limited, 0, N * sizeof(int), st));
+    return WBC_OK;
+  }
+  LimitArgs<T> a;
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.Jc = (const T*)out->Jc; a.wdes = (const T*)in->w_des;
+  a.rhat = s->params.observer_order > 0 ? (const T*)obs->r : nullptr;
+  a.normals = (const T*)in->normals; a.mu = (const T*)in->mu; a.mask = in->mask;
+  a.tau = (T*)out->tau; a.f = (T*)out->f; a.status = out->status; a.iters = out->iters; a.limited = limited;
+  a.list = s->d_limit; a.jpack = s->jpack;
+  for (int i = 0; i < 12; ++i) a.lim[i] = s->tau_max[s->jmap.j[i]];
+  const wbc_params& p = s->params;
+  for (int i = 0; i < 6; ++i) a.S[i] = p.S[i];
+  a.alpha = p.alpha; a.fn_min = p.fn_min; a.fn_max = p.fn_max; a.mu_scale = p.mu_scale; a.tol = p.qp_tol; a.max_iter = p.max_iter;
+  HIP_TRY(hipMemsetAsync(s->d_limit, 0, sizeof(int), st));
+  LaunchCtx L; L.st = st;
+  hipError_t e = k_limit_scan<T>(L, a);
+  if (e == hipSuccess) e = k_limit_qp<T>(L, a, s->limit_grid);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("torque-limit launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
+extern "C" int wbc_limit_torques_batch(wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs,
+                                       int* limited, void* stream) {
+  const int rc0 = check_limit_args(s, N, in, out, obs);
+  if (rc0) return rc0;
+  if (N == 0) return WBC_OK;
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64 ? limit_impl<double>(s, N, in, out, obs, limited, st) : limit_impl<float>(s, N, in, out, obs, limited, st);
+}
+
+extern "C" int wbc_step_limited_batch(wbc_solver* s, size_t N, const wbc_batch_in* in, const wbc_batch_out* out, const wbc_observer_state* obs,
+                                      int* limited, void* stream) {
+  int rc = check_step_args(s, N, in, out, obs, false);   // every check of both halves before anything is enqueued
+  if (rc) return rc;
+  rc = check_limit_args(s, N, in, out, obs);
+  if (rc) return rc;
+  rc = wbc_step_batch(s, N, in, out, obs, stream);
+  if (rc) return rc;
+  return wbc_limit_torques_batch(s, N, in, out, obs, limited, stream);
+}
+
+// diagnostics: how many states the LAST post-pass listed for a re-solve (synchronises)
+extern "C" int wbc_solver_limited_count(wbc_solver* s, int* resolved) {
+  if (!s || !resolved) return fail(WBC_E_INVALID, "null argument");
+  if (s->limit_skipped) { *resolved = 0; return WBC_OK; }
+  ON_DEVICE(s);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(resolved, s->d_limit, sizeof(int), hipMemcpyDeviceToHost));
+  return WBC_OK;
 }
 
 template <class T>
