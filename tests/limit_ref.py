@@ -146,12 +146,14 @@ def integrate(P, dyn, tau, f, q, v):
         q[s, 7:] += dt * v[s, 6:]
 
 
-def swing_case(total_mass, n=64):
-    """Trot masks; the swing legs are asked for joint accelerations large enough that their torques pass 45 N m."""
+def swing_case(total_mass, n=64, legs=None):
+    """Trot masks; the swing legs are asked for joint accelerations large enough that their torques pass 45 N m.  legs = leg_joints(flat) of a model
+    whose joint order is not leg-major (default: foot k's leg is joints 3 k ... 3 k + 2)."""
     B = synth.make_batch(3, n, total_mass, rank=3)
     B["vdot_des"] = B["vdot_des"].copy()
     for s in range(n):
         for k in range(4):
             if not (B["mask"][s] >> k) & 1:
-                B["vdot_des"][s, 6 + 3 * k:9 + 3 * k] = 2500.0 * (1 if (s + k) % 2 else -1)
+                js = [3 * k, 3 * k + 1, 3 * k + 2] if legs is None else legs[k]
+                B["vdot_des"][s, [6 + j for j in js]] = 2500.0 * (1 if (s + k) % 2 else -1)
     return B

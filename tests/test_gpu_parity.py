@@ -8,7 +8,7 @@ PARITY UNPINNED against the reference itself (source absent) -- see DESIGN.md.
 import numpy as np
 import pytest
 
-from tests.util import elementwise_excess, relerr, to_dev, to_host, unpack_M
+from tests.util import elementwise_excess, permuted_urdf as _permuted_urdf, relerr, to_dev, to_host, unpack_M
 from wbc_quadruped_dob_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -465,25 +465,6 @@ def test_empty_shard_is_a_no_op_everywhere(torch_cuda, gpu_model):
     for fm in (0, -1):   # ... whichever dispatch the solver would pick
         s2, _ = _solver(gpu_model, obs=0, max_batch=8, options={"fused_max": fm, "rollout_persistent": 0})
         assert L.wbc_rollout_batch(s2._h, 0, 3, C.byref(bi), C.byref(bo), None, None, None, None) == 0
-
-
-def _permuted_urdf(tmp_path):
-    """Same robot, different document order: legs interleaved and listed back-to-front, so that neither the joint
-    order (q/v components) nor the foot order is leg-major any more."""
-    import re
-    import wbc_quadruped_dob_amd as W
-    txt = open(W.SYNTHETIC_URDF).read()
-    head, rest = txt.split('<link name="front_left_hip">', 1)
-    rest = '<link name="front_left_hip">' + rest.replace("</robot>", "")
-    # split the four leg sections
-    legs = {}
-    for name in ("front_left", "front_right", "back_left", "back_right"):
-        m = re.search(r'(<link name="%s_hip">.*?<joint name="%s_foot_joint" type="fixed">.*?</joint>\n)' % (name, name), rest, re.S)
-        legs[name] = m.group(1)
-    out = head + legs["back_right"] + legs["front_left"] + legs["back_left"] + legs["front_right"] + "</robot>\n"
-    p = tmp_path / "permuted.urdf"
-    p.write_text(out)
-    return str(p)
 
 
 def test_permuted_joint_and_foot_order(torch_cuda, tmp_path):

@@ -58,19 +58,90 @@ def test_reference_is_sound(gpu_model, flat_model, cfg, lim):
     assert len(one) == COUNTS[(cfg, lim)] and not (o["limited"] == 2).any()
     assert np.all(o["status"][one] == 0)
     assert np.all(np.abs(o["tick"]["tau"][o["limited"] == 0]) <= lim)
-    worst = 0.0
-    for s in one:
-        H, g, Cm, d, x, lam = o["qp"][s]
-        scale = max(1.0, np.abs(x).max())
-        stat = np.abs(H @ x + g - Cm.T @ lam).max() / scale
-        slack = Cm @ x - d
-        assert stat < 1e-7 and slack.min() > -1e-6 and lam.min() >= 0 and np.abs(lam * slack).max() / scale < 1e-7, (s, stat, slack.min())
-        stance = [j for k in range(4) if (B["mask"][s] >> k) & 1 for j in legs[k]]
-        worst = max(worst, (np.abs(o["tau"][s, stance]) - lim).max())
-        # the rewritten torque is the torque map of the new forces: tau = tau_tick + (Jc^T (f_tick - f_new))_joint rows
-        J = o["dyn"]["Jc"][s].reshape(12, 18)
-        assert np.abs(o["tau"][s] - (o["tick"]["tau"][s] + J[:, 6:].T @ (o["tick"]["f"][s] - o["f"][s]))).max() < 1e-9
+    worst = max(_check_resolved_state(o, s, B["mask"][s], legs, np.full(12, lim)) for s in one)
     assert worst <= P["qp_tol"], worst
+
+
+def _check_resolved_state(o, s, mask, legs, lim):
+    """One re-solved state of limit_ref.step_limited(..., want_qp=True) against the conditions that define its result; lim [12] in the caller's joint
+    order.  Returns the largest excess of a stance torque over its own joint's limit."""
+    H, g, Cm, d, x, lam = o["qp"][s]
+    scale = max(1.0, np.abs(x).max())
+    stat = np.abs(H @ x + g - Cm.T @ lam).max() / scale
+    slack = Cm @ x - d
+    assert stat < 1e-7 and slack.min() > -1e-6 and lam.min() >= 0 and np.abs(lam * slack).max() / scale < 1e-7, (s, stat, slack.min())
+    stance = [j for k in range(4) if (mask >> k) & 1 for j in legs[k]]
+    # a joint without a limit contributes no rows
+    finite = [j for j in stance if np.isfinite(lim[j])]
+    assert Cm.shape[0] == 2 * len(stance) + 2 * len(finite) and len(x) == len(stance)
+    # the rewritten torque is the torque map of the new forces: tau = tau_tick + (Jc^T (f_tick - f_new))_joint rows
+    J = o["dyn"]["Jc"][s].reshape(12, 18)
+    assert np.abs(o["tau"][s] - (o["tick"]["tau"][s] + J[:, 6:].T @ (o["tick"]["f"][s] - o["f"][s]))).max() < 1e-9
+    return (np.abs(o["tau"][s, finite]) - lim[finite]).max() if finite else -np.inf
+
+
+# states re-solved on the reordered models (tests/limit_models.py), measured with the oracle when these cases were specified:
+# (model, vector, kind, cfg, n, dtype, obs) -> count, or (count, (with 2, 3, 4 stance feet))
+COUNTS_MODELS = {
+    ("G", "a", "trot", 3, 65, "f64", 0): 17, ("G", "a", "trot", 3, 257, "f64", 0): (69, (39, 26, 4)), ("G", "a", "trot", 4, 65, "f64", 0): 19,
+    ("G", "a", "trot", 4, 257, "f64", 0): 72, ("G", "a", "trot", 4, 257, "f32", 1): 65,
+    ("G", "b", "trot", 3, 257, "f64", 0): 166, ("G", "b", "trot", 4, 257, "f64", 0): 167, ("G", "b", "trot", 4, 257, "f32", 1): 164,
+    ("G", "c", "trot", 3, 257, "f64", 1): 149, ("G", "c", "trot", 3, 257, "f32", 1): 149,
+    ("G", "c", "trot", 4, 257, "f64", 1): (149, (57, 74, 18)), ("G", "c", "trot", 4, 257, "f32", 1): (149, (57, 74, 18)),
+    ("G", "a", "one", 4, 64, "f64", 0): 31, ("G", "c", "one", 4, 64, "f32", 1): 24,
+    ("P", "b", "trot", 3, 257, "f64", 0): (155, (59, 74, 22)), ("P", "b", "trot", 4, 257, "f64", 0): (161, (59, 84, 18)),
+    ("P", "b", "trot", 4, 257, "f32", 1): 160,
+    ("P", "c", "trot", 3, 257, "f64", 0): (89, (52, 32, 5)), ("P", "c", "trot", 4, 257, "f64", 0): (96, (53, 38, 5)),
+    ("P", "c", "trot", 4, 65, "f64", 1): 21, ("P", "c", "trot", 4, 257, "f32", 1): (76, (49, 24, 3)),
+    ("P", "b", "one", 4, 64, "f64", 0): 48, ("P", "c", "one", 4, 64, "f64", 0): 45,
+}
+
+
+@pytest.fixture(scope="module")
+def models(hip_lib, tmp_path_factory):
+    from tests import limit_models
+    return limit_models.specs(tmp_path_factory.mktemp("limit_models"))
+
+
+def test_the_reordered_models_are_reordered(models):
+    """Neither model's joint map is the identity, and on G the model's own limits leave every knee free."""
+    for spec in models.values():
+        assert [j for l in spec.legs for j in l] != list(range(12)) and sorted(j for l in spec.legs for j in l) == list(range(12))
+    G = models["G"]
+    assert G.legs == [[3, 4, 5], [9, 10, 11], [6, 7, 8], [0, 1, 2]]
+    a = G.vector("a")
+    assert [x == (np.inf if nm.endswith("_knee") else 55.0) for nm, x in zip(G.joint_names, a)] == [True] * 12
+    for spec in models.values():
+        b, c = spec.vector("b", 1.0), spec.vector("c", 1.0)
+        assert len(set(b)) == 12 and b.min() == 30.0 and b.max() == 52.0
+        free = np.flatnonzero(np.isinf(c))
+        assert len(free) == 5 and np.array_equal(c[np.isfinite(c)], b[np.isfinite(c)])
+        # the gaps sit at a different position on different legs, and one leg has two
+        assert sorted(sorted(l.index(j) for j in free if j in l) for l in spec.legs) == [[0], [0, 1], [1], [2]]
+
+
+@pytest.mark.parametrize("key", sorted(COUNTS_MODELS), ids=lambda k: "-".join(str(x) for x in k))
+def test_reference_is_sound_on_reordered_models(models, key):
+    """test_reference_is_sound's conditions with per-joint and partly infinite limits on models whose joint and foot order is not leg-major, and with one
+    stance foot: KKT residuals at the same gates, every stance torque within ITS joint's limit, the torque map, no rows for a joint without a limit,
+    and the pinned counts."""
+    from tests import limit_models
+    m, which, kind, cfg, n, dtype, obs = key
+    spec = models[m]
+    B, _, _, lim, o = limit_models.case(spec, which, kind, cfg, n, dtype, obs, True)
+    limit_models.check_conditions(spec, which, kind, n, B, lim, o)
+    one = np.flatnonzero(o["limited"] == 1)
+    want = COUNTS_MODELS[key]
+    count, by_feet = want if isinstance(want, tuple) else (want, None)
+    assert len(one) == count and not (o["limited"] == 2).any()
+    ns = limit_models.stance_count(B["mask"])
+    if by_feet is not None:
+        assert tuple(int((ns[one] == k).sum()) for k in (2, 3, 4)) == by_feet
+    assert np.all(o["status"][one] == 0) and np.all(o["qp_status"][one] == 0)
+    assert np.all(np.abs(o["tick"]["tau"][o["limited"] == 0].astype(np.float64)) <= lim)
+    if dtype == "f64":   # (the fp32 reference rounds the fp64 solution of the limited QP: its residual gates are the fp64 run's)
+        worst = max(_check_resolved_state(o, s, int(B["mask"][s]), spec.legs, lim) for s in one)
+        assert worst <= synth.default_params()["qp_tol"], worst
 
 
 def test_constructed_clamp_cases_exist_in_the_reference(gpu_model, oracle, flat_model):

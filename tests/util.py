@@ -42,6 +42,75 @@ def to_host(t):
     return t.detach().cpu().numpy().T.copy()
 
 
+# ---- the torque-limit post-pass on the GPU (tests/test_gpu_limit.py, tests/test_gpu_limit_models.py)
+def _nd(dtype):
+    return np.float64 if dtype == "f64" else np.float32
+
+
+def _obs_state(oracle, B, dtype, obs):
+    if not obs:
+        return None, None
+    n = B["q"].shape[0]
+    integ = oracle.dynamics(B["q"], B["v"], nthreads=8)["p"] - 0.02
+    r = 0.2 * np.cos(np.arange(n * 18).reshape(n, 18))
+    return np.ascontiguousarray(integ, _nd(dtype)), np.ascontiguousarray(r, _nd(dtype))
+
+
+class Dev:
+    """The batch on the device; every call gets fresh output and observer buffers."""
+
+    def __init__(self, torch, B, dtype, integ=None, r=None):
+        self.torch, self.td = torch, torch.float64 if dtype == "f64" else torch.float32
+        self.a = {k: to_dev(B[k], torch, self.td) for k in ("q", "v", "w_des", "vdot_des", "normals", "mu", "tau_prev", "f_prev")}
+        self.mask = torch.from_numpy(np.ascontiguousarray(B["mask"])).to(torch.int32).cuda()
+        self.integ, self.r = integ, r
+
+    def obs(self):
+        if self.integ is None:
+            return None, None
+        return to_dev(self.integ, self.torch, self.td), to_dev(self.r, self.torch, self.td)
+
+    def args(self, ig, rr):
+        a = self.a
+        return (a["q"], a["v"], a["w_des"], a["vdot_des"], a["normals"], a["mu"], self.mask, a["tau_prev"], a["f_prev"], ig, rr)
+
+    def step_limited(self, solver, out=None):
+        ig, rr = self.obs()
+        out = solver.step_limited(*self.args(ig, rr), out=out)
+        out["obs_r"] = rr
+        return out
+
+    def step(self, solver, **kw):
+        ig, rr = self.obs()
+        out = solver.step(*self.args(ig, rr), want_mats=True, **kw)
+        out["obs_r"] = rr
+        return out
+
+
+def _host(torch, out):
+    torch.cuda.synchronize()
+    return {k: (to_host(v) if v.dim() == 2 else v.cpu().numpy()) for k, v in out.items() if v is not None}
+
+
+def _compare(got, ref, dtype, lim, keep=None):
+    """limited and status integer for integer; tau and f at the gates of tests/test_gpu_parity.py's default-option cases (fp64: 1e-6 of every entry,
+    elementwise_excess; fp32: 5e-4 of the largest entry).  States whose largest |tau| sits within 1e-9 (fp32: 1e-3 x limit) of the limit may be
+    classified either way and are left out: at most 5 % of a case."""
+    band = 1e-9 if dtype == "f64" else 1e-3 * float(np.min(lim))
+    use = ref["margin"] >= band
+    assert use.mean() >= 0.95, use.mean()
+    if dtype == "f64":
+        assert use.all()
+    if keep is not None:
+        use = use & keep
+    np.testing.assert_array_equal(got["limited"][use], ref["limited"][use])
+    np.testing.assert_array_equal(got["status"][use], ref["status"][use])
+    gate = dict(rtol=1e-6, atol_frac=1e-9) if dtype == "f64" else dict(rtol=0.0, atol_frac=5e-4)
+    et, ef = elementwise_excess(got["tau"][use], ref["tau"][use], **gate), elementwise_excess(got["f"][use], ref["f"][use], **gate)
+    print("limited", np.bincount(ref["limited"][use], minlength=3), "excess tau %.3g f %.3g" % (et, ef))
+    assert et <= 1.0 and ef <= 1.0, (et, ef)
+
+
 def random_problem(rng, n, m, meq, cond=1e3):
     """A feasible strictly convex QP (H, g, C, d) with m rows, the first meq of them equalities: H = Q diag(1 .. cond) Q^T, rows of C
     random with a third of the inequalities tight or violated at the unconstrained minimum, feasibility guaranteed by construction
@@ -56,3 +125,22 @@ def random_problem(rng, n, m, meq, cond=1e3):
     d = C @ xf - slack
     g = -H @ (xf + rng.normal(size=n) * 2.0)     # the unconstrained minimum sits away from the feasible point
     return H, g, C, d
+
+
+def permuted_urdf(tmp_path):
+    """Same robot, different document order: legs interleaved and listed back-to-front, so that neither the joint
+    order (q/v components) nor the foot order is leg-major any more."""
+    import re
+    import wbc_quadruped_dob_amd as W
+    txt = open(W.SYNTHETIC_URDF).read()
+    head, rest = txt.split('<link name="front_left_hip">', 1)
+    rest = '<link name="front_left_hip">' + rest.replace("</robot>", "")
+    # split the four leg sections
+    legs = {}
+    for name in ("front_left", "front_right", "back_left", "back_right"):
+        m = re.search(r'(<link name="%s_hip">.*?<joint name="%s_foot_joint" type="fixed">.*?</joint>\n)' % (name, name), rest, re.S)
+        legs[name] = m.group(1)
+    out = head + legs["back_right"] + legs["front_left"] + legs["back_left"] + legs["front_right"] + "</robot>\n"
+    p = tmp_path / "permuted.urdf"
+    p.write_text(out)
+    return str(p)
