@@ -53,6 +53,12 @@ struct ComPlan {              // input of the CoM planner (wbc_reference_batch's
   double duration;            // s; <= 0 = hold the goal
   double quat_des_xyzw[4];    // desired trunk attitude
 };
+struct SwingPlan {            // one foot's row of wbc_swing_reference_batch's swing plan
+  double liftoff[3], touchdown[3];   // world
+  double clearance;           // apex height above the straight line, m
+  double duration;            // s; <= 0 = hold the touchdown point
+  double elapsed;             // s already spent in this swing at t = 0
+};
 struct Command {              // what the planner hands to the tick
   double w_des[6];            // desired contact wrench on the base rows
   std::array<double, 18> vdot_des;
@@ -128,6 +134,30 @@ class QuadrupedWBC {
     for (int k = 0; k < 4; ++k) row[8 + k] = cp.quat_des_xyzw[k];
     Command c;
     check(wbc_compute_reference(solver_, q.data(), v.data(), row, t, c.w_des, c.vdot_des.data(), com_out), "wbc_compute_reference");
+    return c;
+  }
+
+  // Swing-foot references (wbc_hip.h, "Swing-foot references"): Cartesian tracking for the feet that contacts.stance marks as lifted.
+  // swingReference(): cmd.vdot_des comes from plan() (or the caller); the lifted legs' joint rows are replaced by the foot-tracking law.
+  // referenceSwing(): plan() followed by swingReference().  foot_out (24, optional): p_f (3) and J_k v (3) of all four feet.
+  void setSwingGains(const wbc_swing_params& p) { check(wbc_solver_set_swing_params(solver_, &p), "wbc_solver_set_swing_params"); }
+  void swingReference(const BaseState& base, const JointState& js, const ContactState& contacts, const std::array<SwingPlan, 4>& sp, double t,
+                      Command& cmd, double* foot_out = nullptr) {
+    std::vector<double> q, v;
+    packState(base, js, q, v);
+    double row[WBC_SWING_WORDS];
+    int mask = 0;
+    for (int f = 0; f < 4; ++f) {
+      if (contacts.stance[f]) mask |= 1 << f;
+      for (int k = 0; k < 3; ++k) { row[9 * f + k] = sp[f].liftoff[k]; row[9 * f + 3 + k] = sp[f].touchdown[k]; }
+      row[9 * f + 6] = sp[f].clearance; row[9 * f + 7] = sp[f].duration; row[9 * f + 8] = sp[f].elapsed;
+    }
+    check(wbc_compute_swing_reference(solver_, q.data(), v.data(), mask, row, t, cmd.vdot_des.data(), foot_out), "wbc_compute_swing_reference");
+  }
+  Command referenceSwing(const BaseState& base, const JointState& js, const ContactState& contacts, const ComPlan& cp,
+                         const std::array<SwingPlan, 4>& sp, double t, double* com_out = nullptr, double* foot_out = nullptr) {
+    Command c = plan(base, js, cp, t, com_out);
+    swingReference(base, js, contacts, sp, t, c, foot_out);
     return c;
   }
 

@@ -428,6 +428,52 @@ int wbc_step_limited_batch(wbc_solver* s, size_t N, const wbc_batch_in* in, cons
 /* diagnostics (synchronises the device): how many states the last post-pass re-solved */
 int wbc_solver_limited_count(wbc_solver* s, int* resolved);
 
+/* Swing-foot references: Cartesian foot tracking for swing legs.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct changes; detect it
+ * by these symbols).  wbc_reference_batch asks a lifted leg only for the joint posture law; these calls replace that leg's rows of vdot_des by the joint
+ * accelerations that make its foot follow a planned trajectory, which the tick then turns into the leg's inverse-dynamics torque.
+ *   swing [WBC_SWING_WORDS = 36][N], solver scalar type, component-major; foot k owns rows 9k .. 9k+8:
+ *     9k .. 9k+2  p0   lift-off position (world)          9k+6  hgt  apex clearance, m
+ *     9k+3 .. +5  p1   touchdown position (world)         9k+7  T    swing duration, s        9k+8  t0  time already elapsed, s
+ *   u = clamp((t0 + t) / T, 0, 1)   (T <= 0: u = 1),  d = p1 - p0,  z = (0, 0, 1)
+ *   s0, s1, s2: the rest-to-rest quintic of wbc_reference_batch and its first two time derivatives (factors 1/T, 1/T^2; 0 when T <= 0)
+ *   b = 64 u^3 (1-u)^3,   b' = 192 u^2 (1-u)^2 (1-2u),   b'' = 384 u (1-u) (1 - 5u + 5u^2)
+ *   p_ref = p0 + s0 d + hgt b z,   pd_ref = s1 d + hgt b'/T z,   pdd_ref = s2 d + hgt b''/T^2 z      (every derivative term is 0 at u = 0 and u = 1)
+ * For every foot k whose bit in `mask` is CLEAR, with J_k = foot k's three rows of Jc = [J_kb (3x6) | J_kl (3x3, the leg's own joint columns)]:
+ *   a_cmd = pdd_ref + kp o (p_ref - p_f) + kd o (pd_ref - J_k v)
+ *   rhs   = a_cmd - Jdot_k v - J_kb vdot_des[0..5]
+ *   (J_kl J_kl^T + damping 1) y = rhs,      vdot_des[6 + j] = (J_kl^T y)_j   for the three joints j of leg k, caller's joint order
+ * Jdot_k v is the foot point's world acceleration at vdot = 0 (velocity-product recursion down the leg); it equals d/de [J_k(q (+) e v)] v at e = 0 with
+ * (+) the configuration update of wbc_integrate_batch.  vdot_des[0..5] are read as they stand on entry (typically wbc_reference_batch has just written
+ * them).  Rows of stance legs, the base rows and w_des are not touched, bit for bit; a caller who wants the posture law for a lifted leg sets that leg's
+ * bit in the mask passed to THIS call.  Damped least squares is used for every state, not only next to a singularity: the result is continuous in q.
+ * foot (optional) [WBC_FOOT_WORDS = 24][N]: rows 6k .. 6k+2 = p_f, 6k+3 .. 6k+5 = J_k v, for ALL four feet.
+ * Stream rules as for wbc_reference_batch (the two batch calls): no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without
+ * looking at the buffers; a NULL required pointer: WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
+ * Out of scope: the one-launch rollout kernels and wbc_rollout_*, wbc_multi_*, contact schedules and touchdown detection, an apex direction aligned
+ * with the terrain normal. */
+#define WBC_SWING_WORDS 36
+#define WBC_FOOT_WORDS 24
+typedef struct wbc_swing_params {
+  size_t struct_size;    /* sizeof(wbc_swing_params) of the caller's build */
+  double kp[3], kd[3];   /* world axes, >= 0 */
+  double damping;        /* lambda^2, m^2, >= 0 */
+} wbc_swing_params;
+/* kp = 400, kd = 40 (critically damped), damping = 1e-4: this build's definition, as wbc_ref_params_default is */
+void wbc_swing_params_default(wbc_swing_params* p);
+/* a negative or non-finite entry: WBC_E_INVALID.  The values travel as a kernel argument: nothing is uploaded, later swing calls use them.
+ * Not inside a stream capture (a captured graph keeps the values it was captured with). */
+int wbc_solver_set_swing_params(wbc_solver* s, const wbc_swing_params* p);
+int wbc_swing_reference_batch(wbc_solver* s, size_t N, const void* q, const void* v, const int* mask, const void* swing, double t,
+                              void* vdot_des /* in/out */, void* foot, void* stream);
+/* wbc_reference_batch followed by wbc_swing_reference_batch, as ONE launch.  w_des, com, the base rows and the stance legs' rows of vdot_des are
+ * bit-identical to wbc_reference_batch's; the swing legs' rows equal the two-call sequence's to rounding (not bit for bit: DESIGN.md 4.10). */
+int wbc_reference_swing_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, const int* mask, const void* swing,
+                              double t, void* w_des, void* vdot_des, void* com, void* foot, void* stream);
+/* Single-robot, host-pointer, fp64 form of wbc_swing_reference_batch (q[19], v[18], swing[36] in; vdot_des[18] in/out; the optional foot[24] out):
+ * the companion of wbc_compute_reference.  Synchronises. */
+int wbc_compute_swing_reference(wbc_solver* s, const double* q, const double* v, int mask, const double* swing, double t,
+                                double* vdot_des /* in/out */, double* foot);
+
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
  * synchronises.  obs_integ/obs_r (host, nv each) are in/out and may be NULL when the observer is off. */

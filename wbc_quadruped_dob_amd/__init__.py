@@ -249,6 +249,14 @@ def lib():
             L.wbc_limit_torques_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
             L.wbc_step_limited_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
             L.wbc_solver_limited_count.argtypes = [C.c_void_p, C.c_void_p]
+        # swing-foot references: additive to ABI 10, detected by the symbols in the same way (_swing_lib)
+        if hasattr(L, "wbc_swing_reference_batch"):
+            L.wbc_swing_params_default.argtypes = [C.c_void_p]
+            L.wbc_swing_params_default.restype = None
+            L.wbc_solver_set_swing_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_swing_reference_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 3
+            L.wbc_reference_swing_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 5
+            L.wbc_compute_swing_reference.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -275,6 +283,14 @@ def _limit_lib():
     L = lib()
     if not hasattr(L, "wbc_step_limited_batch"):
         raise RuntimeError("%s lacks the torque-limit entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+def _swing_lib():
+    """lib(), for the swing-foot reference calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_swing_reference_batch"):
+        raise RuntimeError("%s lacks the swing-reference entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     return L
 
 
@@ -322,6 +338,36 @@ class ScoreParams(C.Structure):
                 setattr(p, k, float(val))
             else:
                 raise KeyError("ScoreParams has no field %r" % k)
+        return p
+
+
+SWING_WORDS = 36   # include/wbc_hip.h: WBC_SWING_WORDS -- swing [SWING_WORDS, N]: per foot k rows 9 k ...: p0 (3), p1 (3), hgt, T, t0
+FOOT_WORDS = 24    # include/wbc_hip.h: WBC_FOOT_WORDS -- foot [FOOT_WORDS, N]: per foot k rows 6 k ...: p_f (3), J_k v (3)
+
+
+class SwingParams(C.Structure):
+    """wbc_swing_params: the gains of the swing-foot references (include/wbc_hip.h)"""
+    _fields_ = [("struct_size", C.c_size_t), ("kp", C.c_double * 3), ("kd", C.c_double * 3), ("damping", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = SwingParams()
+        _swing_lib().wbc_swing_params_default(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d):
+        """keys kp, kd (scalars broadcast over the world axes), damping; missing keys keep the defaults (400, 40, 1e-4)"""
+        p = SwingParams.default()
+        for k, val in d.items():
+            if k in ("kp", "kd"):
+                a = np.broadcast_to(np.asarray(val, dtype=np.float64), (3,))
+                for i in range(3):
+                    getattr(p, k)[i] = float(a[i])
+            elif k == "damping":
+                p.damping = float(val)
+            else:
+                raise KeyError("SwingParams has no field %r" % k)
         return p
 
 
@@ -751,6 +797,56 @@ class Solver:
                                          self._ptr(out["com"], 6, N) if want_com else None, self._stream()),
                "wbc_reference_batch")
         return out
+
+    def set_swing_params(self, p):
+        """p: SwingParams or dict (see SwingParams.from_dict): the gains of every later swing-reference call of this solver."""
+        if isinstance(p, dict):
+            p = SwingParams.from_dict(p)
+        _check(_swing_lib().wbc_solver_set_swing_params(self._h, C.byref(p)), "wbc_solver_set_swing_params")
+
+    def swing_reference(self, q, v, mask, swing, t=0.0, vdot_des=None, want_foot=False):
+        """Swing-foot references (wbc_swing_reference_batch): for every foot whose mask bit is clear, the leg's joint rows of vdot_des [nv, N] are
+        REPLACED IN PLACE by the joint accelerations that track the foot trajectory of swing [SWING_WORDS, N] at time t; the base rows are read as
+        they stand, everything else is left alone.  Returns dict(vdot_des[, foot [FOOT_WORDS, N]])."""
+        m = self.model
+        N = q.shape[1]
+        assert vdot_des is not None, "vdot_des is in/out: pass the tensor reference() filled"
+        out = dict(vdot_des=vdot_des)
+        if want_foot:
+            out["foot"] = self.torch.empty((FOOT_WORDS, N), dtype=self.tdtype, device=q.device)
+        _check(_swing_lib().wbc_swing_reference_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(mask, 1, N, self.torch.int32),
+                                                      self._ptr(swing, SWING_WORDS, N), C.c_double(t), self._ptr(vdot_des, m.nv, N),
+                                                      self._ptr(out.get("foot"), FOOT_WORDS, N), self._stream()), "wbc_swing_reference_batch")
+        return out
+
+    def reference_swing(self, q, v, plan, mask, swing, t=0.0, out=None, want_com=False, want_foot=False):
+        """reference() followed by swing_reference(), as one launch (wbc_reference_swing_batch):
+        dict(w_des [6, N], vdot_des [nv, N][, com [6, N]][, foot [FOOT_WORDS, N]])."""
+        torch = self.torch
+        m = self.model
+        N = q.shape[1]
+        out = {} if out is None else out
+        for k, rows in (("w_des", 6), ("vdot_des", m.nv)) + ((("com", 6),) if want_com else ()) + ((("foot", FOOT_WORDS),) if want_foot else ()):
+            if k not in out:
+                out[k] = torch.empty((rows, N), dtype=self.tdtype, device=q.device)
+        _check(_swing_lib().wbc_reference_swing_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(plan, PLAN_WORDS, N),
+                                                      self._ptr(mask, 1, N, torch.int32), self._ptr(swing, SWING_WORDS, N), C.c_double(t),
+                                                      self._ptr(out["w_des"], 6, N), self._ptr(out["vdot_des"], m.nv, N),
+                                                      self._ptr(out["com"], 6, N) if want_com else None,
+                                                      self._ptr(out["foot"], FOOT_WORDS, N) if want_foot else None, self._stream()),
+               "wbc_reference_swing_batch")
+        return out
+
+    def compute_swing_reference(self, q, v, mask, swing, vdot_des, t=0.0):
+        """Single-robot host-array form of swing_reference (numpy float64, fp64 solvers): returns (vdot_des[nv] with the swing legs' rows replaced,
+        foot[FOOT_WORDS]); the argument vdot_des is not modified."""
+        d = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        q, v, swing = d(q), d(v), d(swing)
+        vd, foot = np.array(vdot_des, dtype=np.float64), np.zeros(FOOT_WORDS)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(_swing_lib().wbc_compute_swing_reference(self._h, p(q), p(v), int(mask), p(swing), C.c_double(t), p(vd), p(foot)),
+               "wbc_compute_swing_reference")
+        return vd, foot
 
     def rollout_tracking(self, horizon, q, v, plan, normals, mu, mask, out, w_des, vdot_des, obs_integ=None, obs_r=None,
                          tau_ext=None, tau_traj=None, com_traj=None, payload=None):

@@ -16,10 +16,13 @@
 
 namespace wbc {
 
+// SWING (swing_ref.hip.hpp, wbc_reference_swing_batch): a functor that replaces the posture law of the lane's leg where the leg swings, from what this body
+// holds in registers anyway (R, E, the base rows of vdot_des).  RefNoSwing (every kernel but com_swing_reference_kernel): no call, no code.
+struct RefNoSwing { static constexpr bool on = false; };
 // EXT (persistent rollout kernel, fused_tick.hip.hpp): one wavefront of a larger workgroup, tables already in LDS.
-template <class T, bool EXT, int SPW = 16, bool SIMG = false>   // SIMG: role of a rollout workgroup that keeps states / plans / references in LDS
+template <class T, bool EXT, int SPW = 16, bool SIMG = false, class SWING = RefNoSwing>   // SIMG: role of a rollout workgroup that keeps states / plans / references in LDS
 WBC_DEV void com_reference_body(const DevModel<T>* __restrict__ model, const DevRefParams<T>* __restrict__ G, const RefArgs<T>& a,
-                                const T* cst_ext) {
+                                const T* cst_ext, const SWING& swing = SWING()) {
   __shared__ T cst_own[EXT ? 1 : CST_WORDS];
   if constexpr (!EXT) {
     for (int i = threadIdx.x; i < CST_WORDS; i += blockDim.x) cst_own[i] = model->cst[i];
@@ -157,6 +160,7 @@ WBC_DEV void com_reference_body(const DevModel<T>* __restrict__ model, const Dev
   T adj[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) adj[k] = G->kp_joint * (G->q_nom[jx[k]] - ql[k]) - G->kd_joint * vl[k];
+  if constexpr (SWING::on) swing(cst, leg, N, s32, live, R, qb, vb, om0, E, vl, acmd, alcmd, a.t, adj);
   bool to_mem = true;
   if constexpr (SIMG) {   // the rnea role of the same workgroup reads the references in LDS (its caller raises a flag behind an LDS-only fence)
     T* const ri = a.refimg + (si_ - a.simg);

@@ -187,6 +187,25 @@ template <class T> struct RefArgs {
   int skip_out;               // (likewise) 1: w_des, vdot_des go to the LDS image only -- every tick of a launch but the last
 };
 
+// swing-foot references (swing_ref.hip.hpp): the gains and what a call reads and writes -- kernel arguments BY VALUE, so a call neither uploads
+// nor allocates (hipGraph-capturable; wbc_solver_set_swing_params only fills the solver's host copy)
+constexpr int SWING_WORDS = 36;   // swing [SWING_WORDS][N]: per foot k rows 9 k ...: p0 (3), p1 (3), hgt, T, t0
+constexpr int FOOT_WORDS = 24;    // foot [FOOT_WORDS][N]: per foot k rows 6 k ...: p_f (3), J_k v (3)
+template <class T> struct DevSwingParams { T kp[3], kd[3], damping; };
+template <class T> struct SwingArgs {
+  const int* mask; const T* swing;
+  T* foot;   // [FOOT_WORDS][N] or null
+  DevSwingParams<T> P;
+};
+template <class T> struct SwingRefArgs {   // the stand-alone kernel (the fused one takes RefArgs + SwingArgs)
+  size_t N;
+  const T* q; const T* v;
+  T t;
+  T* vdot_des;   // in (base rows) / out (joint rows of the swing legs)
+  unsigned long long jpack;   // see SweepArgs::jpack
+  SwingArgs<T> s;
+};
+
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc
 constexpr int SW_STEP = 2;  // write the step workspace (d, b, taup, JcL)

@@ -128,5 +128,9 @@ template <class T> hipError_t k_integrate(const LaunchCtx& L, const DevModel<T>*
 // integrate_kernel<T, true>: k_integrate with a payload [10][N] on the plant's trunk (integrate.hip.hpp, PAYLOAD; defined in the payload unit of k_rollout.hip)
 template <class T> hipError_t k_integrate_plant(const LaunchCtx& L, const DevModel<T>* model, const IntegrateArgs<T>& a, const T* payload);
 template <class T> hipError_t k_reference(const LaunchCtx& L, const DevModel<T>* model, const DevRefParams<T>* G, const RefArgs<T>& a);
+// swing-foot references (swing_ref.hip.hpp): swing_reference_kernel<T> rewrites the swing legs' rows of a.vdot_des from its base rows as they stand;
+// com_swing_reference_kernel<T> is k_reference with the same law applied before its joint rows are stored -- one launch
+template <class T> hipError_t k_swing_reference(const LaunchCtx& L, const DevModel<T>* model, const SwingRefArgs<T>& a);
+template <class T> hipError_t k_reference_swing(const LaunchCtx& L, const DevModel<T>* model, const DevRefParams<T>* G, const RefArgs<T>& a, const SwingArgs<T>& sa);
 
 }  // namespace wbc

@@ -58,6 +58,7 @@ struct wbc_model { FlatModel fm; };
 constexpr size_t TIMING_MAX_SPANS = 4096;   // bounded ring: samples beyond it are dropped until the next collect
 constexpr int ONE_SCRATCH = 200;        // first scalar of the helpers' scratch region of the single-robot image (88 scalars)
 constexpr int ONE_SCALARS = 288;        // scalars in front of the image's ints (the tick uses the first 161)
+constexpr int SWING_ONE_SCALARS = 19 + 18 + 36 + 18 + 24;   // wbc_compute_swing_reference: q v swing | vdot_des | foot, then one int (the mask)
 
 // thresholds between kernel variants after the options are applied (resolve_options)
 constexpr long long WBC_OBS_SPLIT_MIN_NOMATS_F64 = 16384;
@@ -90,6 +91,8 @@ struct wbc_solver {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   void* d_ref = nullptr;     // DevRefParams<T>, set by wbc_solver_set_ref_params
   wbc_score_params score;    // the weights of the scored rollouts (wbc_solver_set_score_params; kernel arguments by value), defaults at creation
+  wbc_swing_params swing;    // the gains of the swing-foot references (wbc_solver_set_swing_params; kernel arguments by value), defaults at creation
+  void* d_swing_one = nullptr;   // wbc_compute_swing_reference's staging: SWING_ONE_SCALARS scalars + the mask
   // torque-limit post-pass (wbc_limit_torques_batch): the limits travel as a kernel argument like the score weights
   double tau_max[WBC_MAXV];  // caller's joint order, HUGE_VAL = none; the model's effort limits at creation
   double model_effort[WBC_MAXV];
@@ -665,6 +668,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   if (!s) return fail(WBC_E_INVALID, "out of memory");
   s->dtype = dtype; s->device = device; s->max_batch = max_batch; s->params = *p; s->opt = o;
   wbc_score_params_default(&s->score);
+  wbc_swing_params_default(&s->swing);
   for (int j = 0; j < WBC_MAXV; ++j) s->model_effort[j] = (j < m->fm.nj() && j < (int)m->fm.effort_limit.size()) ? m->fm.effort_limit[j] : HUGE_VAL;
   std::memcpy(s->tau_max, s->model_effort, sizeof(s->tau_max));
   s->limit_grid = limit_qp_grid(prop.multiProcessorCount);
@@ -702,6 +706,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   if (e == hipSuccess) e = hipHostGetDevicePointer(&s->h_one_dev, s->h_one, 0);
   // (the completion ticket lives in this image: a recycled pinned block must not look like ticket 1 of a solver whose first tick is still running)
   if (e == hipSuccess) { std::memset(s->h_one, 0, s->one_bytes); e = hipMemset(s->d_one, 0, s->one_bytes); }
+  if (e == hipSuccess) e = hipMalloc(&s->d_swing_one, SWING_ONE_SCALARS * sizeof(double) + sizeof(int));
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->aux, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming);
@@ -733,6 +738,7 @@ extern "C" void wbc_solver_destroy(wbc_solver* s) {
   if (s->d_one) (void)hipFree(s->d_one);
   if (s->h_one) (void)hipHostFree(s->h_one);
   if (s->d_ref) (void)hipFree(s->d_ref);
+  if (s->d_swing_one) (void)hipFree(s->d_swing_one);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);
   if (s->aux) (void)hipStreamDestroy(s->aux);
@@ -1435,6 +1441,84 @@ extern "C" int wbc_reference_batch(wbc_solver* s, size_t N, const void* q, const
                              : reference_impl<float>(s, N, q, v, plan, t, w_des, vdot_des, com, st);
 }
 
+// ---- swing-foot references: the gains, the stand-alone call, the CoM reference generator with the swing law fused in
+extern "C" void wbc_swing_params_default(wbc_swing_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  for (int i = 0; i < 3; ++i) { p->kp[i] = 400; p->kd[i] = 40; }   // critically damped
+  p->damping = 1e-4;
+}
+
+extern "C" int wbc_solver_set_swing_params(wbc_solver* s, const wbc_swing_params* p) {
+  if (!s || !p) return fail(WBC_E_INVALID, "null argument");
+  if (p->struct_size < sizeof(wbc_swing_params)) return fail(WBC_E_INVALID, "wbc_swing_params: struct_size too small (call wbc_swing_params_default first)");
+  const double w[] = {p->kp[0], p->kp[1], p->kp[2], p->kd[0], p->kd[1], p->kd[2], p->damping};
+  for (double x : w)
+    if (!(x >= 0) || !std::isfinite(x)) return fail(WBC_E_INVALID, "wbc_swing_params: gains and damping must be finite and non-negative");
+  s->swing = *p;
+  return WBC_OK;
+}
+
+template <class T>
+static void swing_args(SwingArgs<T>& a, const wbc_solver* s, const int* mask, const void* swing, void* foot) {
+  std::memset(&a, 0, sizeof(a));
+  a.mask = mask; a.swing = (const T*)swing; a.foot = (T*)foot;
+  for (int i = 0; i < 3; ++i) { a.P.kp[i] = (T)s->swing.kp[i]; a.P.kd[i] = (T)s->swing.kd[i]; }
+  a.P.damping = (T)s->swing.damping;
+}
+
+template <class T>
+static int swing_reference_impl(wbc_solver* s, size_t N, const void* q, const void* v, const int* mask, const void* swing, double t, void* vdot_des,
+                                void* foot, hipStream_t st) {
+  SwingRefArgs<T> a;
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.t = (T)t; a.vdot_des = (T*)vdot_des; a.jpack = s->jpack;
+  swing_args(a.s, s, mask, swing, foot);
+  LaunchCtx L; L.st = st;
+  hipError_t e = k_swing_reference<T>(L, dev_model<T>(s), a);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("swing reference launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
+extern "C" int wbc_swing_reference_batch(wbc_solver* s, size_t N, const void* q, const void* v, const int* mask, const void* swing, double t,
+                                         void* vdot_des, void* foot, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !mask || !swing || !vdot_des) return fail(WBC_E_INVALID, "null argument");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64 ? swing_reference_impl<double>(s, N, q, v, mask, swing, t, vdot_des, foot, st)
+                             : swing_reference_impl<float>(s, N, q, v, mask, swing, t, vdot_des, foot, st);
+}
+
+template <class T>
+static int reference_swing_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, const int* mask, const void* swing, double t,
+                                void* w_des, void* vdot_des, void* com, void* foot, hipStream_t st) {
+  RefArgs<T> a;
+  ref_args(a, s, N, q, v, plan, t, w_des, vdot_des, com);
+  SwingArgs<T> sa;
+  swing_args(sa, s, mask, swing, foot);
+  LaunchCtx L; L.st = st;
+  hipError_t e = k_reference_swing<T>(L, dev_model<T>(s), (const DevRefParams<T>*)s->d_ref, a, sa);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("reference + swing launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
+extern "C" int wbc_reference_swing_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, const int* mask, const void* swing,
+                                         double t, void* w_des, void* vdot_des, void* com, void* foot, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !plan || !mask || !swing || !w_des || !vdot_des) return fail(WBC_E_INVALID, "null argument");
+  if (!s->d_ref) return fail(WBC_E_INVALID, "call wbc_solver_set_ref_params first");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64 ? reference_swing_impl<double>(s, N, q, v, plan, mask, swing, t, w_des, vdot_des, com, foot, st)
+                             : reference_swing_impl<float>(s, N, q, v, plan, mask, swing, t, w_des, vdot_des, com, foot, st);
+}
+
 // ---- scored rollouts: the weights, the superset rollout, one tick's cost, the per-group selection
 extern "C" void wbc_score_params_default(wbc_score_params* p) {
   if (!p) return;
@@ -1666,6 +1750,29 @@ extern "C" int wbc_compute_reference(wbc_solver* s, const double* q, const doubl
       dst[i] = s->dtype == WBC_F64 ? ((double*)hb)[o + i] : (double)((float*)hb)[o + i];
   };
   get(off[3], w_des, 6); get(off[4], vdot_des, 18); get(off[5], com, 6);
+  return WBC_OK;
+}
+
+// Single-robot, host-pointer form of wbc_swing_reference_batch: staged through the solver's own device block (the pinned image's scratch region is too
+// small for the 36 plan words), pageable copies on the null stream.
+extern "C" int wbc_compute_swing_reference(wbc_solver* s, const double* q, const double* v, int mask, const double* swing, double t, double* vdot_des,
+                                           double* foot) {
+  if (!s || !q || !v || !swing || !vdot_des) return fail(WBC_E_INVALID, "null argument");
+  if (s->dtype != WBC_F64) return fail(WBC_E_INVALID, "wbc_compute_swing_reference: fp64 solvers only");
+  ON_DEVICE(s);
+  double h[SWING_ONE_SCALARS];
+  const int oq = 0, ov = 19, os = 37, oa = 73, of = 91;
+  std::memcpy(h + oq, q, 19 * sizeof(double)); std::memcpy(h + ov, v, 18 * sizeof(double));
+  std::memcpy(h + os, swing, SWING_WORDS * sizeof(double)); std::memcpy(h + oa, vdot_des, 18 * sizeof(double));
+  double* d = (double*)s->d_swing_one;
+  int* dmask = (int*)(d + SWING_ONE_SCALARS);
+  HIP_TRY(hipMemcpy(d, h, of * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dmask, &mask, sizeof(int), hipMemcpyHostToDevice));
+  int rc = wbc_swing_reference_batch(s, 1, d + oq, d + ov, dmask, d + os, t, d + oa, d + of, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(h + oa, d + oa, (18 + FOOT_WORDS) * sizeof(double), hipMemcpyDeviceToHost));
+  std::memcpy(vdot_des, h + oa, 18 * sizeof(double));
+  if (foot) std::memcpy(foot, h + of, FOOT_WORDS * sizeof(double));
   return WBC_OK;
 }
 
