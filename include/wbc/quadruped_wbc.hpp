@@ -59,6 +59,17 @@ struct SwingPlan {            // one foot's row of wbc_swing_reference_batch's s
   double duration;            // s; <= 0 = hold the touchdown point
   double elapsed;             // s already spent in this swing at t = 0
 };
+struct GaitCommand {          // one robot's row of wbc_gait_batch's cmd
+  double vx, vy;              // commanded trunk velocity, heading frame, m/s
+  double wz;                  // commanded yaw rate, rad/s
+  double ground_z;            // world z of the footholds
+};
+struct GaitState {            // what the gait scheduler carries from tick to tick
+  double phase = 0.0;         // in [0, 1)
+  bool stance[4] = {true, true, true, true};
+  std::array<SwingPlan, 4> swing{};   // elapsed is rewritten every tick: pass t = 0 to swingReference / referenceSwing
+  int events = 0;             // bit k: foot k lifted off on the last tick, bit 4 + k: it touched down
+};
 struct Command {              // what the planner hands to the tick
   double w_des[6];            // desired contact wrench on the base rows
   std::array<double, 18> vdot_des;
@@ -159,6 +170,32 @@ class QuadrupedWBC {
     Command c = plan(base, js, cp, t, com_out);
     swingReference(base, js, contacts, sp, t, c, foot_out);
     return c;
+  }
+
+  // Gait scheduler (wbc_hip.h, "Gait scheduler"): one control period of the phase clock.  gaitParamsDefault(): the default schedule with this model's
+  // hip origins as nominal footholds.  gait(): advances st in place -- the phase, the stance flags, and the plans of the lifted feet (lift-off point
+  // latched, Raibert foothold, elapsed time); sensed[k] = foot k senses ground (nullptr: none does).  The tick is then
+  // gait(), referenceSwing(base, js, contacts with st.stance, cp, st.swing, 0.0), computeTorques().
+  wbc_gait_params gaitParamsDefault() const { wbc_gait_params p; wbc_gait_params_default(model_, &p); return p; }
+  void setGaitParams(const wbc_gait_params& p) { check(wbc_solver_set_gait_params(solver_, &p), "wbc_solver_set_gait_params"); }
+  void gait(const BaseState& base, const JointState& js, const GaitCommand& gc, GaitState& st, const bool* sensed = nullptr) {
+    std::vector<double> q, v;
+    packState(base, js, q, v);
+    const double cmd[WBC_GAIT_CMD_WORDS] = {gc.vx, gc.vy, gc.wz, gc.ground_z};
+    double row[WBC_SWING_WORDS];
+    int mask = 0, contact = 0;
+    for (int f = 0; f < 4; ++f) {
+      if (st.stance[f]) mask |= 1 << f;
+      if (sensed && sensed[f]) contact |= 1 << f;
+      for (int k = 0; k < 3; ++k) { row[9 * f + k] = st.swing[f].liftoff[k]; row[9 * f + 3 + k] = st.swing[f].touchdown[k]; }
+      row[9 * f + 6] = st.swing[f].clearance; row[9 * f + 7] = st.swing[f].duration; row[9 * f + 8] = st.swing[f].elapsed;
+    }
+    check(wbc_compute_gait(solver_, q.data(), v.data(), cmd, contact, &st.phase, &mask, row, &st.events), "wbc_compute_gait");
+    for (int f = 0; f < 4; ++f) {
+      st.stance[f] = ((mask >> f) & 1) != 0;
+      for (int k = 0; k < 3; ++k) { st.swing[f].liftoff[k] = row[9 * f + k]; st.swing[f].touchdown[k] = row[9 * f + 3 + k]; }
+      st.swing[f].clearance = row[9 * f + 6]; st.swing[f].duration = row[9 * f + 7]; st.swing[f].elapsed = row[9 * f + 8];
+    }
   }
 
   // Joint torque limits (wbc_hip.h, "Joint torque limits behind a tick").  effortLimits(): the URDF's <limit effort> per joint in jointNames() order,

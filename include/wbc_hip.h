@@ -474,6 +474,68 @@ int wbc_reference_swing_batch(wbc_solver* s, size_t N, const void* q, const void
 int wbc_compute_swing_reference(wbc_solver* s, const double* q, const double* v, int mask, const double* swing, double t,
                                 double* vdot_des /* in/out */, double* foot);
 
+/* Gait scheduler: contact masks, footholds and swing plans on the device.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct changes;
+ * detect it by these symbols).  The swing calls above take `mask` and the 36 `swing` words from the caller; this call writes them, so that a walking
+ * tick is four launches on one stream with no host work between them:  gait -> reference_swing -> step -> integrate.
+ *   cmd [WBC_GAIT_CMD_WORDS = 4][N], solver scalar type, component-major: rows 0, 1 the commanded trunk velocity vx, vy in the HEADING frame, row 2 the
+ *         commanded yaw rate wz, row 3 the ground height z_g (world z of the foothold)
+ *   phase [N]  in/out: the gait phase phi in [0, 1)
+ *   mask [N]   in: the previous tick's mask (before the first tick the caller stores 0b1111);  out: this tick's mask
+ *   swing [WBC_SWING_WORDS][N]  in/out: the plan words of wbc_swing_reference_batch.  This call writes t0 itself, so the swing call behind it is given t = 0
+ *   contact [N] or NULL: bit k set = foot k senses ground (NULL: no bit set)
+ *   events [N] or NULL: bit k set = foot k lifted off this tick, bit 4 + k set = it touched down this tick
+ * With dt the solver's control period the host forms, in double, rounded to the solver's scalar type and passed as kernel arguments:
+ *   dphi = dt / period,   inv_sw[k] = 1 / (1 - duty[k])  (0 when duty[k] == 1),   T_sw[k] = (1 - duty[k]) period
+ * Per state:
+ *   1. phi' = phi + dphi;  if phi' >= 1: phi' -= 1.  phi' is stored.
+ *   2. per foot k:  phi_k = phi' + offset[k];  if phi_k >= 1: phi_k -= 1;   sched_k = phi_k < duty[k];   u_k = (phi_k - duty[k]) inv_sw[k]  (used only
+ *      when !sched_k)
+ *   3. the new bit from the previous bit b_k and the sensed bit c_k:
+ *        sched_k              -> 1
+ *        !sched_k, b_k == 1   -> 1 if u_k >= late (a stance foot that finds itself late in its swing window stays down: it missed its lift-off or landed
+ *                                  early), else 0: a LIFT-OFF
+ *        !sched_k, b_k == 0   -> 1 if c_k and u_k >= late (an early touchdown), else 0
+ *   4. the nine swing words of foot k:
+ *        new bit 1            all nine untouched, bit for bit
+ *        lift-off             p0 = the foot's current world position p_f(q),  hgt = clearance,  T = T_sw[k],  t0 = u_k T_sw[k],  p1 = the foothold
+ *        continuing swing     t0 = u_k T_sw[k];  p1 = the foothold when retarget;  p0, hgt, T untouched, bit for bit
+ *   5. the foothold (Raibert: where the nominal foothold will be at touchdown + half a stance of commanded travel + velocity feedback).  With
+ *      h = (R00, R10) of the base rotation, normalised (the heading; undefined when the trunk's x axis is vertical), Rz the 2x2 rotation it defines:
+ *        b = Rz base_xy[k],   v_c = Rz (vx, vy),   v = v[0..1],   T_rem = (1 - u_k) T_sw[k],   T_st = duty[k] period
+ *        p1_xy = p_b,xy + b + v T_rem + 1/2 T_st v_c + k_v (v - v_c) + 1/2 T_st wz (-b_y, b_x),      p1_z = z_g
+ * Only additions, subtractions and comparisons -- and the single rounded product u_k, which no compiler can contract -- decide the mask: mask, events and
+ * every word this call leaves untouched are EXACT (the same bits as the same arithmetic on a CPU in the same scalar type).  p0, p1 and t0 are exact only to
+ * rounding, because the compiler may contract their products.
+ * Stream rules as for wbc_swing_reference_batch: no allocation, no synchronisation, hipGraph-capturable; phase, mask and swing advance IN PLACE; N == 0
+ * returns WBC_OK without looking at the buffers; a NULL required pointer: WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
+ * Out of scope: the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown (the schedule says stance and no contact is sensed); terrain-normal
+ * footholds; fusing this call into the fused reference + swing kernel, whose fp64 instantiation already uses 256 VGPRs and would spill. */
+#define WBC_GAIT_CMD_WORDS 4
+typedef struct wbc_gait_params {
+  size_t struct_size;   /* sizeof(wbc_gait_params) of the caller's build */
+  double period;        /* gait cycle, s, > 0 */
+  double duty[4];       /* stance fraction per foot, 0 < duty <= 1 (1 = never lifts) */
+  double offset[4];     /* phase offset per foot, 0 <= offset < 1 */
+  double clearance;     /* hgt written into the swing plan, m, >= 0 */
+  double k_v;           /* velocity-feedback gain of the foothold, s, finite */
+  double late;          /* 0 < late <= 1: a stance foot lifts only while u < late; sensed contact ends a swing only when u >= late */
+  int    retarget;      /* 1: p1 recomputed every tick of the swing; 0: latched at lift-off */
+  double base_xy[4][2]; /* nominal foothold of foot k relative to the base origin, heading frame, m */
+} wbc_gait_params;
+/* period 0.4, duty 0.6, offset {0, .5, .5, 0} (feet {0, 3} and {1, 2} are the diagonal pairs), clearance 0.05, k_v 0.03, late 0.5, retarget 1;
+ * base_xy[k] = x, y of the origin of the first joint of foot k's leg in the base frame, caller's foot order (zeros when m is NULL or not a quadruped) */
+void wbc_gait_params_default(const wbc_model* m /* may be NULL */, wbc_gait_params* p);
+/* a value outside the ranges above or a non-finite value: WBC_E_INVALID.  The values travel as a kernel argument: nothing is uploaded, later gait calls
+ * use them.  Not inside a stream capture (a captured graph keeps the values it was captured with). */
+int wbc_solver_set_gait_params(wbc_solver* s, const wbc_gait_params* p);
+int wbc_gait_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact /* may be NULL */,
+                   void* phase /* in/out [N] */, int* mask /* in/out [N] */, void* swing /* in/out [36][N] */, int* events /* may be NULL, [N] */,
+                   void* stream);
+/* Single-robot, host-pointer, fp64 form of wbc_gait_batch (q[19], v[18], cmd[4] in; phase[1], mask[1], swing[36] in/out; the optional events[1] out).
+ * Synchronises. */
+int wbc_compute_gait(wbc_solver* s, const double* q, const double* v, const double* cmd, int contact, double* phase, int* mask, double* swing,
+                     int* events);
+
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
  * synchronises.  obs_integ/obs_r (host, nv each) are in/out and may be NULL when the observer is off. */

@@ -257,6 +257,13 @@ def lib():
             L.wbc_swing_reference_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 3
             L.wbc_reference_swing_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 5
             L.wbc_compute_swing_reference.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        # gait scheduler: additive to ABI 10, detected by the symbols in the same way (_gait_lib)
+        if hasattr(L, "wbc_gait_batch"):
+            L.wbc_gait_params_default.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_gait_params_default.restype = None
+            L.wbc_solver_set_gait_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_gait_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
+            L.wbc_compute_gait.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -291,6 +298,14 @@ def _swing_lib():
     L = lib()
     if not hasattr(L, "wbc_swing_reference_batch"):
         raise RuntimeError("%s lacks the swing-reference entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+def _gait_lib():
+    """lib(), for the gait scheduler's calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_gait_batch"):
+        raise RuntimeError("%s lacks the gait-scheduler entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     return L
 
 
@@ -369,6 +384,47 @@ class SwingParams(C.Structure):
             else:
                 raise KeyError("SwingParams has no field %r" % k)
         return p
+
+
+GAIT_CMD_WORDS = 4   # include/wbc_hip.h: WBC_GAIT_CMD_WORDS -- cmd [GAIT_CMD_WORDS, N]: vx, vy (heading frame), wz, z_g
+
+
+class GaitParams(C.Structure):
+    """wbc_gait_params: the schedule and foothold rule of the gait scheduler (include/wbc_hip.h)"""
+    _fields_ = [("struct_size", C.c_size_t), ("period", C.c_double), ("duty", C.c_double * 4), ("offset", C.c_double * 4), ("clearance", C.c_double),
+                ("k_v", C.c_double), ("late", C.c_double), ("retarget", C.c_int), ("base_xy", (C.c_double * 2) * 4)]
+
+    @staticmethod
+    def default(model=None):
+        """wbc_gait_params_default: base_xy from the model's hip origins (zeros without a model)"""
+        p = GaitParams()
+        _gait_lib().wbc_gait_params_default(model._h if model is not None else None, C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d, model=None):
+        """keys period, duty, offset (scalars broadcast over the feet), clearance, k_v, late, retarget, base_xy [4, 2]; missing keys keep the defaults"""
+        p = GaitParams.default(model)
+        for k, val in d.items():
+            if k in ("duty", "offset"):
+                a = np.broadcast_to(np.asarray(val, dtype=np.float64), (4,))
+                for i in range(4):
+                    getattr(p, k)[i] = float(a[i])
+            elif k == "base_xy":
+                a = np.broadcast_to(np.asarray(val, dtype=np.float64), (4, 2))
+                for i in range(4):
+                    p.base_xy[i][0], p.base_xy[i][1] = float(a[i, 0]), float(a[i, 1])
+            elif k == "retarget":
+                p.retarget = int(val)
+            elif k in ("period", "clearance", "k_v", "late"):
+                setattr(p, k, float(val))
+            else:
+                raise KeyError("GaitParams has no field %r" % k)
+        return p
+
+    def as_dict(self):
+        return dict(period=self.period, duty=tuple(self.duty), offset=tuple(self.offset), clearance=self.clearance, k_v=self.k_v, late=self.late,
+                    retarget=self.retarget, base_xy=tuple((r[0], r[1]) for r in self.base_xy))
 
 
 class TorqueLimits(C.Structure):
@@ -473,6 +529,10 @@ class Model:
         lim = np.zeros(self.nj)
         _check(_limit_lib().wbc_model_effort_limits(self._h, lim.ctypes.data_as(C.c_void_p)), "wbc_model_effort_limits")
         return lim
+
+    def gait_params_default(self):
+        """GaitParams.default(self): the default schedule with this model's hip origins as nominal footholds"""
+        return GaitParams.default(self)
 
     def __del__(self):
         try:
@@ -847,6 +907,34 @@ class Solver:
         _check(_swing_lib().wbc_compute_swing_reference(self._h, p(q), p(v), int(mask), p(swing), C.c_double(t), p(vd), p(foot)),
                "wbc_compute_swing_reference")
         return vd, foot
+
+    def set_gait_params(self, p):
+        """p: GaitParams or dict (see GaitParams.from_dict; base_xy defaults to this solver's model): the schedule of every later gait call."""
+        if isinstance(p, dict):
+            p = GaitParams.from_dict(p, self.model)
+        _check(_gait_lib().wbc_solver_set_gait_params(self._h, C.byref(p)), "wbc_solver_set_gait_params")
+
+    def gait(self, q, v, cmd, phase, mask, swing, contact=None, events=None):
+        """Gait scheduler (wbc_gait_batch): phase [N], mask [N] (int32) and swing [SWING_WORDS, N] advance IN PLACE by one control period from the state
+        q, v and the command cmd [GAIT_CMD_WORDS, N]; contact / events: optional int32 [N].  The swing call behind it takes t = 0."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        _check(_gait_lib().wbc_gait_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(cmd, GAIT_CMD_WORDS, N),
+                                          self._ptr(contact, 1, N, i32), self._ptr(phase, 1, N), self._ptr(mask, 1, N, i32),
+                                          self._ptr(swing, SWING_WORDS, N), self._ptr(events, 1, N, i32), self._stream()), "wbc_gait_batch")
+        return dict(phase=phase, mask=mask, swing=swing, events=events)
+
+    def compute_gait(self, q, v, cmd, phase, mask, swing, contact=0):
+        """Single-robot host-array form of gait (numpy float64, fp64 solvers): returns (phase, mask, swing[SWING_WORDS], events); the arguments are
+        not modified."""
+        d = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        q, v, cmd = d(q), d(v), d(cmd)
+        sw, ph = np.array(swing, dtype=np.float64), C.c_double(float(phase))
+        mk, ev = C.c_int(int(mask)), C.c_int(0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(_gait_lib().wbc_compute_gait(self._h, p(q), p(v), p(cmd), int(contact), C.byref(ph), C.byref(mk), p(sw), C.byref(ev)), "wbc_compute_gait")
+        return ph.value, mk.value, sw, ev.value
 
     def rollout_tracking(self, horizon, q, v, plan, normals, mu, mask, out, w_des, vdot_des, obs_integ=None, obs_r=None,
                          tau_ext=None, tau_traj=None, com_traj=None, payload=None):

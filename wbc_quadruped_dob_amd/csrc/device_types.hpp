@@ -206,6 +206,24 @@ template <class T> struct SwingRefArgs {   // the stand-alone kernel (the fused 
   SwingArgs<T> s;
 };
 
+// gait scheduler (gait.hip.hpp): the schedule and what a call reads and writes -- a kernel argument BY VALUE like the swing gains
+// (wbc_solver_set_gait_params only fills the solver's host copy; dphi, inv_sw, T_sw are formed on the host in double and rounded to T)
+constexpr int GAIT_CMD_WORDS = 4;   // cmd [GAIT_CMD_WORDS][N]: vx, vy (heading frame), wz, z_g
+template <class T> struct DevGaitParams {
+  T dphi, period, clearance, k_v, late;
+  T duty[4], offset[4], inv_sw[4], T_sw[4], bx[4], by[4];
+  int retarget;
+};
+template <class T> struct GaitArgs {
+  size_t N;
+  const T* q; const T* v; const T* cmd;
+  const int* contact;   // [N] or null (no foot senses ground)
+  T* phase; int* mask; T* swing;   // in/out
+  int* events;          // [N] or null
+  unsigned long long jpack;   // see SweepArgs::jpack
+  DevGaitParams<T> P;
+};
+
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc
 constexpr int SW_STEP = 2;  // write the step workspace (d, b, taup, JcL)

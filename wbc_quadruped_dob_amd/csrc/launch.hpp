@@ -132,5 +132,7 @@ template <class T> hipError_t k_reference(const LaunchCtx& L, const DevModel<T>*
 // com_swing_reference_kernel<T> is k_reference with the same law applied before its joint rows are stored -- one launch
 template <class T> hipError_t k_swing_reference(const LaunchCtx& L, const DevModel<T>* model, const SwingRefArgs<T>& a);
 template <class T> hipError_t k_reference_swing(const LaunchCtx& L, const DevModel<T>* model, const DevRefParams<T>* G, const RefArgs<T>& a, const SwingArgs<T>& sa);
+// gait scheduler (gait.hip.hpp): gait_kernel<T> advances phase, rewrites mask and the lifted feet's plan words of swing, in place
+template <class T> hipError_t k_gait(const LaunchCtx& L, const DevModel<T>* model, const GaitArgs<T>& a);
 
 }  // namespace wbc

@@ -59,6 +59,7 @@ constexpr size_t TIMING_MAX_SPANS = 4096;   // bounded ring: samples beyond it a
 constexpr int ONE_SCRATCH = 200;        // first scalar of the helpers' scratch region of the single-robot image (88 scalars)
 constexpr int ONE_SCALARS = 288;        // scalars in front of the image's ints (the tick uses the first 161)
 constexpr int SWING_ONE_SCALARS = 19 + 18 + 36 + 18 + 24;   // wbc_compute_swing_reference: q v swing | vdot_des | foot, then one int (the mask)
+constexpr int GAIT_ONE_SCALARS = 19 + 18 + 4 + 1 + 36;      // wbc_compute_gait: q v cmd | phase swing, then three ints (contact, mask, events)
 
 // thresholds between kernel variants after the options are applied (resolve_options)
 constexpr long long WBC_OBS_SPLIT_MIN_NOMATS_F64 = 16384;
@@ -93,6 +94,8 @@ struct wbc_solver {
   wbc_score_params score;    // the weights of the scored rollouts (wbc_solver_set_score_params; kernel arguments by value), defaults at creation
   wbc_swing_params swing;    // the gains of the swing-foot references (wbc_solver_set_swing_params; kernel arguments by value), defaults at creation
   void* d_swing_one = nullptr;   // wbc_compute_swing_reference's staging: SWING_ONE_SCALARS scalars + the mask
+  wbc_gait_params gait;      // the schedule of the gait scheduler (wbc_solver_set_gait_params; kernel arguments by value), the model's defaults at creation
+  void* d_gait_one = nullptr;    // wbc_compute_gait's staging: GAIT_ONE_SCALARS scalars + contact, mask, events
   // torque-limit post-pass (wbc_limit_torques_batch): the limits travel as a kernel argument like the score weights
   double tau_max[WBC_MAXV];  // caller's joint order, HUGE_VAL = none; the model's effort limits at creation
   double model_effort[WBC_MAXV];
@@ -669,6 +672,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   s->dtype = dtype; s->device = device; s->max_batch = max_batch; s->params = *p; s->opt = o;
   wbc_score_params_default(&s->score);
   wbc_swing_params_default(&s->swing);
+  wbc_gait_params_default(m, &s->gait);
   for (int j = 0; j < WBC_MAXV; ++j) s->model_effort[j] = (j < m->fm.nj() && j < (int)m->fm.effort_limit.size()) ? m->fm.effort_limit[j] : HUGE_VAL;
   std::memcpy(s->tau_max, s->model_effort, sizeof(s->tau_max));
   s->limit_grid = limit_qp_grid(prop.multiProcessorCount);
@@ -707,6 +711,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   // (the completion ticket lives in this image: a recycled pinned block must not look like ticket 1 of a solver whose first tick is still running)
   if (e == hipSuccess) { std::memset(s->h_one, 0, s->one_bytes); e = hipMemset(s->d_one, 0, s->one_bytes); }
   if (e == hipSuccess) e = hipMalloc(&s->d_swing_one, SWING_ONE_SCALARS * sizeof(double) + sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&s->d_gait_one, GAIT_ONE_SCALARS * sizeof(double) + 3 * sizeof(int));
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->aux, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming);
@@ -739,6 +744,7 @@ extern "C" void wbc_solver_destroy(wbc_solver* s) {
   if (s->h_one) (void)hipHostFree(s->h_one);
   if (s->d_ref) (void)hipFree(s->d_ref);
   if (s->d_swing_one) (void)hipFree(s->d_swing_one);
+  if (s->d_gait_one) (void)hipFree(s->d_gait_one);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);
   if (s->aux) (void)hipStreamDestroy(s->aux);
@@ -1519,6 +1525,72 @@ extern "C" int wbc_reference_swing_batch(wbc_solver* s, size_t N, const void* q,
                              : reference_swing_impl<float>(s, N, q, v, plan, mask, swing, t, w_des, vdot_des, com, foot, st);
 }
 
+// ---- gait scheduler: the schedule, the batch call (phase, mask and the lifted feet's plan words advance in place)
+extern "C" void wbc_gait_params_default(const wbc_model* m, wbc_gait_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->period = 0.4;
+  const double off[4] = {0.0, 0.5, 0.5, 0.0};   // feet {0, 3} and {1, 2}: the diagonal pairs
+  for (int k = 0; k < 4; ++k) { p->duty[k] = 0.6; p->offset[k] = off[k]; }
+  p->clearance = 0.05; p->k_v = 0.03; p->late = 0.5; p->retarget = 1;
+  int leg_body[4][3];
+  std::string err;
+  if (m && quadruped_topology(m->fm, leg_body, err) == WBC_OK)
+    for (int k = 0; k < 4; ++k) { p->base_xy[k][0] = m->fm.rt[3 * leg_body[k][0]]; p->base_xy[k][1] = m->fm.rt[3 * leg_body[k][0] + 1]; }
+}
+
+extern "C" int wbc_solver_set_gait_params(wbc_solver* s, const wbc_gait_params* p) {
+  if (!s || !p) return fail(WBC_E_INVALID, "null argument");
+  if (p->struct_size < sizeof(wbc_gait_params)) return fail(WBC_E_INVALID, "wbc_gait_params: struct_size too small (call wbc_gait_params_default first)");
+  if (!(p->period > 0) || !std::isfinite(p->period)) return fail(WBC_E_INVALID, "wbc_gait_params: period must be finite and > 0");
+  for (int k = 0; k < 4; ++k) {
+    if (!(p->duty[k] > 0 && p->duty[k] <= 1)) return fail(WBC_E_INVALID, "wbc_gait_params: 0 < duty <= 1");
+    if (!(p->offset[k] >= 0 && p->offset[k] < 1)) return fail(WBC_E_INVALID, "wbc_gait_params: 0 <= offset < 1");
+    if (!std::isfinite(p->base_xy[k][0]) || !std::isfinite(p->base_xy[k][1])) return fail(WBC_E_INVALID, "wbc_gait_params: base_xy must be finite");
+  }
+  if (!(p->clearance >= 0) || !std::isfinite(p->clearance)) return fail(WBC_E_INVALID, "wbc_gait_params: clearance must be finite and >= 0");
+  if (!std::isfinite(p->k_v)) return fail(WBC_E_INVALID, "wbc_gait_params: k_v must be finite");
+  if (!(p->late > 0 && p->late <= 1)) return fail(WBC_E_INVALID, "wbc_gait_params: 0 < late <= 1");
+  if (p->retarget != 0 && p->retarget != 1) return fail(WBC_E_INVALID, "wbc_gait_params: retarget must be 0 or 1");
+  s->gait = *p;
+  return WBC_OK;
+}
+
+template <class T>
+static int gait_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact, void* phase, int* mask, void* swing,
+                     int* events, hipStream_t st) {
+  GaitArgs<T> a;
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.cmd = (const T*)cmd; a.contact = contact;
+  a.phase = (T*)phase; a.mask = mask; a.swing = (T*)swing; a.events = events; a.jpack = s->jpack;
+  const wbc_gait_params& g = s->gait;
+  a.P.dphi = (T)(s->params.dt / g.period); a.P.period = (T)g.period; a.P.clearance = (T)g.clearance; a.P.k_v = (T)g.k_v; a.P.late = (T)g.late;
+  for (int k = 0; k < 4; ++k) {
+    a.P.duty[k] = (T)g.duty[k]; a.P.offset[k] = (T)g.offset[k];
+    a.P.inv_sw[k] = g.duty[k] == 1.0 ? (T)0 : (T)(1.0 / (1.0 - g.duty[k]));
+    a.P.T_sw[k] = (T)((1.0 - g.duty[k]) * g.period);
+    a.P.bx[k] = (T)g.base_xy[k][0]; a.P.by[k] = (T)g.base_xy[k][1];
+  }
+  a.P.retarget = g.retarget;
+  LaunchCtx L; L.st = st;
+  hipError_t e = k_gait<T>(L, dev_model<T>(s), a);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("gait launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
+extern "C" int wbc_gait_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact, void* phase, int* mask,
+                              void* swing, int* events, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !phase || !mask || !swing) return fail(WBC_E_INVALID, "null argument");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64 ? gait_impl<double>(s, N, q, v, cmd, contact, phase, mask, swing, events, st)
+                             : gait_impl<float>(s, N, q, v, cmd, contact, phase, mask, swing, events, st);
+}
+
 // ---- scored rollouts: the weights, the superset rollout, one tick's cost, the per-group selection
 extern "C" void wbc_score_params_default(wbc_score_params* p) {
   if (!p) return;
@@ -1773,6 +1845,31 @@ extern "C" int wbc_compute_swing_reference(wbc_solver* s, const double* q, const
   HIP_TRY(hipMemcpy(h + oa, d + oa, (18 + FOOT_WORDS) * sizeof(double), hipMemcpyDeviceToHost));
   std::memcpy(vdot_des, h + oa, 18 * sizeof(double));
   if (foot) std::memcpy(foot, h + of, FOOT_WORDS * sizeof(double));
+  return WBC_OK;
+}
+
+// Single-robot, host-pointer form of wbc_gait_batch: staged through the solver's own device block like wbc_compute_swing_reference.
+extern "C" int wbc_compute_gait(wbc_solver* s, const double* q, const double* v, const double* cmd, int contact, double* phase, int* mask, double* swing,
+                                int* events) {
+  if (!s || !q || !v || !cmd || !phase || !mask || !swing) return fail(WBC_E_INVALID, "null argument");
+  if (s->dtype != WBC_F64) return fail(WBC_E_INVALID, "wbc_compute_gait: fp64 solvers only");
+  ON_DEVICE(s);
+  double h[GAIT_ONE_SCALARS];
+  const int oq = 0, ov = 19, oc = 37, op = 41, os = 42;
+  std::memcpy(h + oq, q, 19 * sizeof(double)); std::memcpy(h + ov, v, 18 * sizeof(double)); std::memcpy(h + oc, cmd, 4 * sizeof(double));
+  h[op] = *phase; std::memcpy(h + os, swing, SWING_WORDS * sizeof(double));
+  int hi[3] = {contact, *mask, 0};
+  double* d = (double*)s->d_gait_one;
+  int* di = (int*)(d + GAIT_ONE_SCALARS);
+  HIP_TRY(hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(di, hi, sizeof(hi), hipMemcpyHostToDevice));
+  int rc = wbc_gait_batch(s, 1, d + oq, d + ov, d + oc, di, d + op, di + 1, d + os, di + 2, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(h + op, d + op, (1 + SWING_WORDS) * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hi, di, sizeof(hi), hipMemcpyDeviceToHost));
+  *phase = h[op]; std::memcpy(swing, h + os, SWING_WORDS * sizeof(double));
+  *mask = hi[1];
+  if (events) *events = hi[2];
   return WBC_OK;
 }
 
