@@ -30,11 +30,13 @@ def compile_asm(out="/tmp/asm/wbc_lint.s", extra=()):
     concatenated into `out`."""
     os.makedirs(os.path.dirname(out), exist_ok=True)
     csrc = os.path.join(ROOT, "wbc_quadruped_dob_amd", "csrc")
+    # the k_fused units carry flags of their own (kernel-argument preload): taken from the Makefile, so that the lint sees the build that ships
+    unit_flags = {"k_fused": subprocess.check_output(["make", "-s", "--no-print-directory", "-C", csrc, "print-FUSED_FLAGS"], text=True).split()}
     jobs = []
     for unit, defs in KUNITS:
         for scalar in ("double", "float"):
             part = "%s.%s%s.%s.s" % (out, unit, "_track" if defs else "", scalar)
-            cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-DWBC_SCALAR=" + scalar, *defs, *extra, "-S",
+            cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-DWBC_SCALAR=" + scalar, *defs, *unit_flags.get(unit, ()), *extra, "-S",
                    "--cuda-device-only", "-w", "-o", part, unit + ".hip"]
             jobs.append((part, subprocess.Popen(cmd, cwd=csrc)))
     with open(out, "w") as f:

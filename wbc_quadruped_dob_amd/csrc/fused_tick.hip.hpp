@@ -59,11 +59,29 @@ template <class T, bool OBSERVER, bool MATS, bool WARM = false> constexpr bool f
 // fmas in the fp32 tick), so M came out with other last bits than the warm tick, the two-launch tick and every earlier build give -- and those are compared bit for bit
 // (tests/test_gpu_warm.py).  fp64 has no packed arithmetic: its instruction mix, and its bits, are those of the plain-store build.
 template <class T, bool MATS, bool WARM> constexpr int fused_store() { return (MATS && !WARM && sizeof(T) == 8) ? ST_WT : ST_PLAIN; }
+// The QP wavefronts' own stores -- tau, f, status, iters, the active set: the tick's LAST stores -- keep plain stores: write-through there gave +1.5 % at 4 096 fp64
+// states, 2.4 times the parent's run-to-run spread and so short of the gain rule on its own, and cost the observer-on tick 1 % (docs/DESIGN_HISTORY.md).
 template <class T, bool OBSERVER, bool MATS, bool WARM = false> constexpr int fused_threads() { return OBSERVER ? 384 + 64 * FUSED_OBS_WAVES : (fused_split_h<T, OBSERVER, MATS, WARM>() ? 448 : 384); }
 // WARM: the QP of every state starts from the active set in qa.aset_in (wbc_step_batch_warm: dependent ticks of a closed loop)
-template <class T, bool OBSERVER, bool MATS, bool WARM = false>
-__global__ __launch_bounds__((fused_threads<T, OBSERVER, MATS, WARM>()), 1) void fused_tick_kernel(const DevModel<T>* __restrict__ model, DevParams<T> prm,
+// LEAD (observer off: the nine types launch_fused_tick names, k_fused.hip; observer on: empty): leading arguments, ordered by first use, for what the wavefronts need in front of their
+// first memory instruction -- q, v, N, the packed joint indices, vdot_des, w_des (the roles' first loads), mask, normals, mu (the QP wavefronts').  The unit is compiled
+// with kernel-argument preload (csrc/Makefile): the first 14 dwords behind the segment pointer -- model ... w_des -- arrive in scalar registers at wave launch, so the
+// state loads and the table staging no longer start one scalar-memory round trip late; the rest and the structs behind them come by scalar loads that are waited
+// for where first used.  The role bodies keep reading the structs: their fields are patched from the leading arguments (the host passes the same values in both
+// places).  Measured, 4 096 fp64 states, cold, observer off: 339.2 -> 346.3 M steps/s, kernel 12.17 -> 11.86 us.
+// Observer on: no leading arguments.  Those instantiations sit at 251 ... 255 registers, the fourteen more live scalar registers went to vector-register lanes
+// (v_readlane 190 -> 474 in the cold fp64 one) and the tick lost 1 % (docs/DESIGN_HISTORY.md).
+// (after the patch the struct copies of these eleven fields, as loaded from the argument segment, are dead: nothing reads them, and the compiler drops their loads)
+template <class T> WBC_DEV void fused_patch_args(SweepArgs<T>&, QpArgs<T>&) {}
+template <class T> WBC_DEV void fused_patch_args(SweepArgs<T>& a, QpArgs<T>& qa, const T* q, const T* v, size_t N, unsigned long long jpack, const T* vdot_des,
+                                                 const T* w_des, const int* mask, const T* normals, const T* mu) {
+  a.q = q; a.v = v; a.N = N; a.jpack = jpack; a.vdot_des = vdot_des; a.w_des = w_des;
+  qa.N = N; qa.jpack = jpack; qa.mask = mask; qa.normals = normals; qa.mu = mu;
+}
+template <class T, bool OBSERVER, bool MATS, bool WARM = false, class... LEAD>
+__global__ __launch_bounds__((fused_threads<T, OBSERVER, MATS, WARM>()), 1) void fused_tick_kernel(const DevModel<T>* __restrict__ model, LEAD... lead, DevParams<T> prm,
                                                                             SweepArgs<T> a, QpArgs<T> qa, QpJidx jmap) {
+  fused_patch_args<T>(a, qa, lead...);
   __shared__ __attribute__((aligned(512))) T cst[CST_WORDS];   // (the alignment puts the table FIRST in the workgroup's LDS: within reach of the 16-bit ds_read offset, see dyn_sweep.hip.hpp)
   __shared__ int zidx_s[64];
   __shared__ T wsl[WS_LDS_WORDS * 16];

@@ -4,23 +4,36 @@
 
 namespace wbc {
 
+// One instantiation's launch.  Observer off: the kernel's leading arguments (fused_tick.hip.hpp, LEAD) are the first-use fields of the two structs, passed from
+// the structs themselves, so both places always hold the same values; observer on: the structs alone.
+template <class T, bool OBSERVER, bool MATS, bool WARM>
+static void launch_fused_tick(const LaunchCtx& L, const DevModel<T>* model, const DevParams<T>& prm, const SweepArgs<T>& a, const QpArgs<T>& qa, const QpJidx& jmap) {
+  const dim3 grid((unsigned)((a.N + 15) / 16)), block((unsigned)fused_threads<T, OBSERVER, MATS, WARM>());
+  if constexpr (OBSERVER) {
+    WBC_KLAUNCH(L, (fused_tick_kernel<T, true, MATS, WARM>), grid, block, model, prm, a, qa, jmap);
+  } else {
+    using P = const T*;
+    WBC_KLAUNCH(L, (fused_tick_kernel<T, false, MATS, WARM, P, P, size_t, unsigned long long, P, P, const int*, P, P>), grid, block,
+                model, a.q, a.v, a.N, a.jpack, a.vdot_des, a.w_des, qa.mask, qa.normals, qa.mu, prm, a, qa, jmap);
+  }
+}
+
 template <>
 hipError_t k_fused_tick<Scalar>(const LaunchCtx& L, bool observer, bool mats, const DevModel<Scalar>* model, const DevParams<Scalar>& prm,
                                 const SweepArgs<Scalar>& a, const QpArgs<Scalar>& qa, const QpJidx& jmap, bool warm) {
   using T = Scalar;
-  const dim3 grid((unsigned)((a.N + 15) / 16));
-  constexpr unsigned obs_threads = 384 + 64 * FUSED_OBS_WAVES;
+  if (qa.N != a.N || qa.jpack != a.jpack) return hipErrorInvalidValue;   // (the kernel takes one N and one jpack for both structs)
   if (warm) {
-    if (observer && mats) WBC_KLAUNCH(L, (fused_tick_kernel<T, true, true, true>), grid, dim3(obs_threads), model, prm, a, qa, jmap);
-    else if (observer) WBC_KLAUNCH(L, (fused_tick_kernel<T, true, false, true>), grid, dim3(obs_threads), model, prm, a, qa, jmap);
-    else if (mats) WBC_KLAUNCH(L, (fused_tick_kernel<T, false, true, true>), grid, dim3((unsigned)fused_threads<T, false, true, true>()), model, prm, a, qa, jmap);
-    else WBC_KLAUNCH(L, (fused_tick_kernel<T, false, false, true>), grid, dim3(384), model, prm, a, qa, jmap);
+    if (observer && mats) launch_fused_tick<T, true, true, true>(L, model, prm, a, qa, jmap);
+    else if (observer) launch_fused_tick<T, true, false, true>(L, model, prm, a, qa, jmap);
+    else if (mats) launch_fused_tick<T, false, true, true>(L, model, prm, a, qa, jmap);
+    else launch_fused_tick<T, false, false, true>(L, model, prm, a, qa, jmap);
     return hipGetLastError();
   }
-  if (observer && mats) WBC_KLAUNCH(L, (fused_tick_kernel<T, true, true>), grid, dim3(obs_threads), model, prm, a, qa, jmap);
-  else if (observer) WBC_KLAUNCH(L, (fused_tick_kernel<T, true, false>), grid, dim3(obs_threads), model, prm, a, qa, jmap);
-  else if (mats) WBC_KLAUNCH(L, (fused_tick_kernel<T, false, true>), grid, dim3((unsigned)fused_threads<T, false, true>()), model, prm, a, qa, jmap);
-  else WBC_KLAUNCH(L, (fused_tick_kernel<T, false, false>), grid, dim3(384), model, prm, a, qa, jmap);
+  if (observer && mats) launch_fused_tick<T, true, true, false>(L, model, prm, a, qa, jmap);
+  else if (observer) launch_fused_tick<T, true, false, false>(L, model, prm, a, qa, jmap);
+  else if (mats) launch_fused_tick<T, false, true, false>(L, model, prm, a, qa, jmap);
+  else launch_fused_tick<T, false, false, false>(L, model, prm, a, qa, jmap);
   return hipGetLastError();
 }
 
