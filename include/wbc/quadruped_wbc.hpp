@@ -198,6 +198,22 @@ class QuadrupedWBC {
     }
   }
 
+  // Ground-contact plant (wbc_hip.h, "Ground-contact plant"): the contact law's constants, for callers that run the batch calls
+  // wbc_ground_force_batch / wbc_integrate_ground_batch on solver()'s device buffers -- the plant is a simulation-side call and has no single-robot
+  // host-pointer form.  groundParamsDefault(): k_n 2e4, c_n 150, c_t 200, f_touch 5.
+  static wbc_ground_params groundParamsDefault() { wbc_ground_params p; wbc_ground_params_default(&p); return p; }
+  void setGroundParams(const wbc_ground_params& p) { check(wbc_solver_set_ground_params(solver_, &p), "wbc_solver_set_ground_params"); }
+  void groundForce(size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height, const void* mu, void* f_gr,
+                   int* contact = nullptr, void* gap = nullptr, void* stream = nullptr) {
+    check(wbc_ground_force_batch(solver_, N, q, v, Jc, normals, height, mu, f_gr, contact, gap, stream), "wbc_ground_force_batch");
+  }
+  void integrateGround(size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau, const void* normals,
+                       const void* height, const void* mu, const void* tau_ext /* may be nullptr */, void* f_gr, int* contact = nullptr,
+                       void* gap = nullptr, void* stream = nullptr) {   // (the argument order of the C call)
+    check(wbc_integrate_ground_batch(solver_, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, f_gr, contact, gap, stream),
+          "wbc_integrate_ground_batch");
+  }
+
   // Joint torque limits (wbc_hip.h, "Joint torque limits behind a tick").  effortLimits(): the URDF's <limit effort> per joint in jointNames() order,
   // HUGE_VAL where it gives none.  setTorqueLimits(): the limits the post-pass enforces (one value > 0 per joint; empty = back to the URDF's).
   std::vector<double> effortLimits() const {

@@ -536,6 +536,57 @@ int wbc_gait_batch(wbc_solver* s, size_t N, const void* q, const void* v, const 
 int wbc_compute_gait(wbc_solver* s, const double* q, const double* v, const double* cmd, int contact, double* phase, int* mask, double* swing,
                      int* events);
 
+/* Ground-contact plant: terrain reaction forces and sensed foot contact.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct changes;
+ * detect it by these symbols).  wbc_integrate_batch applies the PLANNED ground reaction forces; these calls put a ground under the plant instead, which
+ * pushes back on every foot whatever the controller planned, and they produce the `contact` word wbc_gait_batch reads.  The walking tick becomes
+ *   gait(contact = the previous tick's) -> reference_swing -> step -> integrate_ground          (still four launches, no host work between them).
+ * The law is stateless and handles each foot on its own.  The terrain under foot k is the plane n_k . x = d_k:
+ *   normals [12][N]  the buffer the tick already takes (rows 3k .. 3k+2 = n_k, unit length)
+ *   height  [4][N]   d_k, solver scalar type: one plane offset PER FOOT, so a bump or a hole under a single foot is a different d_k
+ *   mu      [4][N]   the tick's friction coefficients, used UNSCALED (mu_scale belongs to the QP's pyramid and is not applied here)
+ * With lever_k = p_f,k - p_b read from the base-angular columns of this tick's Jc and J_leg,k its own-leg 3x3 block (the words wbc_integrate_batch reads):
+ *   p_f = p_b + lever_k          v_f = pdot_b + omega x lever_k + J_leg,k qdot_leg,k
+ *   phi = n . p_f - d_k          (the gap; negative = penetration)
+ *   v_n = n . v_f                v_t = v_f - v_n n
+ *   f_n = phi < 0 ? max(0, -k_n phi - c_n v_n) : 0
+ *   g   = -c_t v_t
+ *   s   = |g| > mu_k f_n ? mu_k f_n / |g| : 1          (|g| = 0: f_t = 0, no 0/0)
+ *   f_t = s g
+ *   f_gr,k = f_n n + f_t         contact bit k = f_n > f_touch
+ * Outputs: f_gr [12][N] (rows 3k .. 3k+2 = foot k, the rows wbc_integrate_batch reads as f), contact [N] or NULL (bit k = foot k, the encoding of
+ * wbc_gait_batch), gap [4][N] or NULL (phi_k).
+ * wbc_ground_force_batch evaluates the law alone.  wbc_integrate_ground_batch evaluates it and then advances q, v IN PLACE exactly as
+ * wbc_integrate_batch with f = f_gr does, in ONE launch; the force is applied to EVERY foot, the commanded f is no input of the plant at all.
+ * The plant is explicit (the damping term uses the old v), so it is stable only while the damping and the stiffness are small against the foot's
+ * effective mass m_eff = 1 / (n Jc M^-1 Jc^T n) -- well under a kilogram for the synthetic model -- at the solver's dt.  The four feet are coupled
+ * through the trunk: what must stay below 2 is the largest eigenvalue of dt (Jc M^-1 Jc^T) diag(c_t, c_t, c_n) over all twelve foot rows, which is
+ * two to three and a half times the per-foot ratio c_n dt / m_eff (0.97 against 0.45 with the defaults, 2.03 against 0.60 with c_n 200, c_t 500).  The defaults
+ *   k_n = 2e4 N/m,  c_n = 150 N s/m,  c_t = 200 N s/m,  f_touch = 5 N
+ * were fixed on the CPU with the numpy restatement of this law (tests/ground_ref.py) at the solver's default dt = 1e-3: a standing robot released with
+ * its feet 5 mm above flat ground settles to sum_k n . f_gr,k = m_total |g| and a mean penetration of m_total |g| / (4 k_n), and no contact bit
+ * toggles afterwards.  (k_n 2e4, c_n 200, c_t 500 did not pass: that eigenvalue was 2.03 and the foot forces alternated from tick to tick for good;
+ * with the defaults it is 0.97.  tests/test_ground_oracle.py holds the measured settling time, residuals and stability ratios.)  A caller with another
+ * dt or a lighter leg scales c_n, c_t with m_eff / dt.
+ * Known limitation: viscous friction has no stiction -- a foot under a tangential load F creeps at F / c_t.
+ * Stream rules as for wbc_gait_batch: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at the buffers; a NULL
+ * required pointer: WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
+ * Out of scope: the payload plant (wbc_integrate_plant_batch); the rollout kernels and wbc_rollout_*; wbc_multi_*; stiction (a stateful anchor spring);
+ * late touchdown in the gait rule; terrain-normal footholds. */
+typedef struct wbc_ground_params {
+  size_t struct_size;     /* sizeof(wbc_ground_params) of the caller's build */
+  double k_n, c_n, c_t;   /* N/m, N s/m, N s/m; all >= 0 and finite */
+  double f_touch;         /* N, >= 0 */
+} wbc_ground_params;
+void wbc_ground_params_default(wbc_ground_params* p);
+/* a negative or non-finite value: WBC_E_INVALID.  The values travel as a kernel argument: nothing is uploaded, later ground calls use them.  Not inside a
+ * stream capture (a captured graph keeps the values it was captured with). */
+int wbc_solver_set_ground_params(wbc_solver* s, const wbc_ground_params* p);
+int wbc_ground_force_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height,
+                           const void* mu, void* f_gr, int* contact /* may be NULL */, void* gap /* may be NULL */, void* stream);
+int wbc_integrate_ground_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
+                               const void* normals, const void* height, const void* mu, const void* tau_ext /* may be NULL */, void* f_gr,
+                               int* contact /* may be NULL */, void* gap /* may be NULL */, void* stream);
+
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
  * synchronises.  obs_integ/obs_r (host, nv each) are in/out and may be NULL when the observer is off. */

@@ -1,0 +1,418 @@
+"""GPU: the ground-contact plant (wbc_ground_force_batch, wbc_integrate_ground_batch) through the C-ABI against the numpy restatement
+tests/ground_ref.py: parity in both scalar types on ragged sizes over every branch of the contact law, the one-launch plant against the two launches it
+replaces and against the reference, ground far below, models whose joint and foot order is not leg-major, argument checks, a captured four-call tick and
+the walking closed loop with sensed contact fed back to the gait scheduler.
+
+Gates.  contact: exact.  f_gr, gap, q, v -- fp64: 1e-6 of every entry (util.elementwise_excess, the project's gate).  fp32: tests/ground_ref.py
+evaluated in float32 against float64 on this file's parity cases (sizes 1, 15, 16, 17, 33), error relative to the largest entry of the array:
+f_gr 1.1e-5, gap 1.3e-5, q 6.5e-8, v 3.7e-7 (ground_ref.F32_ERR, measured on the CPU and checked by tests/test_ground_oracle.py; f_gr and gap carry the
+cancellation n . p_f - d of numbers of 0.4 m to a gap of millimetres).  The device contracts products and has its own square root, so the gates are
+8 x those.  integrate_ground against the reference: the integrator's existing gates, 1e-9 (fp64) and 1e-4 (fp32) of the largest entry
+(tests/test_gpu_envelope.py)."""
+import functools
+
+import numpy as np
+import pytest
+
+from tests import gait_ref as GR, ground_ref as R, limit_models, limit_ref, swing_ref as SR
+from tests.util import elementwise_excess, relerr, to_dev, to_host
+from wbc_quadruped_dob_amd import synth
+
+pytestmark = pytest.mark.gpu
+SIZES = R.PARITY_SIZES
+F32_GATE = {k: 8 * e for k, e in R.F32_ERR.items()}
+TIGHT64, F32_DYN = 1e-9, 1e-4     # the integrator's gates of tests/test_gpu_envelope.py
+DT = 1e-3                         # synth.default_params' control period
+INPUTS = ("q", "v", "normals", "height", "mu", "tau", "tau_ext")
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "GPU test run without a GPU"
+    return torch
+
+
+def _solver(model, dtype="f64", max_batch=64, dt=None, ground=None, ref_params=None, gait=None, swing=None):
+    import wbc_quadruped_dob_amd as W
+    P = synth.default_params(observer_order=0, dtype=dtype)
+    if dt is not None:
+        P["dt"] = dt
+    s = W.Solver(model, W.Params.from_dict(P, dtype), dtype=dtype, device=0, max_batch=max_batch)
+    if ground is not None:
+        s.set_ground_params(ground)
+    if ref_params is not None:
+        s.set_ref_params(ref_params)
+    if gait is not None:
+        s.set_gait_params({k: (np.asarray(v) if k in ("duty", "offset", "base_xy") else v) for k, v in gait.items()})
+    if swing is not None:
+        s.set_swing_params(swing)
+    return s
+
+
+_FLATS = {}
+
+
+def _register(name, flat, total_mass):
+    _FLATS[name] = (flat, total_mass)
+    return name
+
+
+@functools.lru_cache(maxsize=None)
+def _case(flat_id, n):
+    """(case, reference: q', v', ground_force's dict, in float64): computed once per (model, size), read only"""
+    flat, tm = _FLATS[flat_id]
+    c = R.branch_case(flat, tm, n, rank=n)
+    ref = R.integrate_ground(R.params(), DT, c["dyn"], c["tau"], c["normals"], c["height"], c["mu"], c["tau_ext"], c["q"], c["v"],
+                             limit_ref.leg_joints(flat))
+    return c, ref
+
+
+def _td(torch, dtype):
+    return torch.float64 if dtype == "f64" else torch.float32
+
+
+def _dev_case(torch, c, dtype):
+    td = _td(torch, dtype)
+    d = {k: to_dev(c[k], torch, td) for k in INPUTS}
+    d.update({k: to_dev(c["dyn"][k], torch, td) for k in ("M", "h", "Jc")})
+    return d
+
+
+def _outs(torch, n, dtype):
+    """outputs prefilled with recognisable junk: a word the call does not write shows"""
+    td = _td(torch, dtype)
+    return dict(f_gr=torch.full((12, n), 7.5, dtype=td, device="cuda"), contact=torch.full((n,), -1, dtype=torch.int32, device="cuda"),
+                gap=torch.full((4, n), 7.5, dtype=td, device="cuda"))
+
+
+def _force(torch, solver, d, o):
+    solver.ground_force(d["q"], d["v"], d["Jc"], d["normals"], d["height"], d["mu"], f_gr=o["f_gr"], contact=o["contact"], gap=o["gap"])
+    torch.cuda.synchronize()
+    return dict(f_gr=to_host(o["f_gr"]), contact=o["contact"].cpu().numpy(), gap=to_host(o["gap"]))
+
+
+def _plant(torch, solver, d, o, q, v):
+    solver.integrate_ground(q, v, d["M"], d["h"], d["Jc"], d["tau"], d["normals"], d["height"], d["mu"], tau_ext=d["tau_ext"], f_gr=o["f_gr"],
+                            contact=o["contact"], gap=o["gap"])
+    torch.cuda.synchronize()
+    return dict(f_gr=to_host(o["f_gr"]), contact=o["contact"].cpu().numpy(), gap=to_host(o["gap"]), q=to_host(q), v=to_host(v))
+
+
+def _gate(got, ref, dtype, what, n):
+    ex = elementwise_excess(got, ref) if dtype == "f64" else elementwise_excess(got, ref, rtol=0.0, atol_frac=F32_GATE[what])
+    print("%s %s n=%d: excess %.3g (max |ref| %.3g, max |diff| %.3g)" % (what, dtype, n, ex, np.abs(ref).max(), np.abs(np.asarray(got, np.float64) - ref).max()))
+    assert np.all(np.isfinite(got)), what
+    assert ex <= 1.0, (what, ex)
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("n", SIZES)
+def test_ground_force_parity_over_every_branch(torch_cuda, gpu_model, flat_model, dtype, n):
+    torch = torch_cuda
+    fid = _register("synthetic", flat_model, gpu_model.total_mass)
+    c, (_, _, g) = _case(fid, n)
+    if n >= 15:
+        assert R.branches_taken(R.params(), g) == R.ALL_BRANCHES
+    solver = _solver(gpu_model, dtype, max_batch=n)
+    got = _force(torch, solver, _dev_case(torch, c, dtype), _outs(torch, n, dtype))
+    assert np.array_equal(got["contact"], g["contact"])
+    _gate(got["f_gr"], g["f_gr"], dtype, "f_gr", n)
+    _gate(got["gap"], g["gap"], dtype, "gap", n)
+    rest = c["kinds"][:, 0] == -1
+    if rest.any():      # v_t = 0 exactly: finite (asserted above) and no tangential force at all
+        assert np.array_equal(got["f_gr"][rest][:, [0, 1, 3, 4, 6, 7, 9, 10]], np.zeros((rest.sum(), 8)))
+    # contact and gap are optional
+    o = _outs(torch, n, dtype)
+    d = _dev_case(torch, c, dtype)
+    solver.ground_force(d["q"], d["v"], d["Jc"], d["normals"], d["height"], d["mu"], f_gr=o["f_gr"], want_contact=False)
+    torch.cuda.synchronize()
+    assert np.array_equal(to_host(o["f_gr"]), got["f_gr"])
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("n", SIZES)
+def test_integrate_ground_equals_force_then_integrate_and_the_reference(torch_cuda, gpu_model, flat_model, dtype, n):
+    """One launch against the two it replaces (ground_force -> integrate(f = f_gr)) on the same inputs, and against ground_ref."""
+    torch = torch_cuda
+    fid = _register("synthetic", flat_model, gpu_model.total_mass)
+    c, (q_ref, v_ref, g) = _case(fid, n)
+    solver = _solver(gpu_model, dtype, max_batch=n)
+    d = _dev_case(torch, c, dtype)
+    two = _force(torch, solver, d, _outs(torch, n, dtype))
+    q2, v2 = d["q"].clone(), d["v"].clone()
+    solver.integrate(q2, v2, d["M"], d["h"], d["Jc"], d["tau"], to_dev(two["f_gr"], torch, _td(torch, dtype)), d["tau_ext"])
+    torch.cuda.synchronize()
+    two.update(q=to_host(q2), v=to_host(v2))
+    one = _plant(torch, solver, d, _outs(torch, n, dtype), d["q"].clone(), d["v"].clone())
+    assert np.array_equal(one["contact"], two["contact"]) and np.array_equal(one["contact"], g["contact"])
+    for k in ("f_gr", "gap", "q", "v"):
+        _gate(one[k], two[k].astype(np.float64), dtype, k, n)
+    print("integrate_ground %s n=%d bit-identical to ground_force -> integrate: %s" % (dtype, n, all(np.array_equal(one[k], two[k]) for k in ("f_gr", "gap", "q", "v"))))
+    # against the reference
+    _gate(one["f_gr"], g["f_gr"], dtype, "f_gr", n)
+    _gate(one["gap"], g["gap"], dtype, "gap", n)
+    eq, ev = relerr(one["q"], q_ref), relerr(one["v"], v_ref)
+    print("integrate_ground %s n=%d against ground_ref: q %.3g v %.3g" % (dtype, n, eq, ev))
+    tol = TIGHT64 if dtype == "f64" else F32_DYN
+    assert eq < tol and ev < tol
+    assert not np.array_equal(one["q"], c["q"].astype(one["q"].dtype))
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("n", SIZES)
+def test_ground_far_below_is_integrate_with_zero_force(torch_cuda, gpu_model, flat_model, dtype, n):
+    torch = torch_cuda
+    fid = _register("synthetic", flat_model, gpu_model.total_mass)
+    c, _ = _case(fid, n)
+    solver = _solver(gpu_model, dtype, max_batch=n)
+    d = _dev_case(torch, c, dtype)
+    d["height"] = torch.full_like(d["height"], -10.0)
+    q, v = d["q"].clone(), d["v"].clone()
+    got = _plant(torch, solver, d, _outs(torch, n, dtype), q, v)
+    assert np.array_equal(got["f_gr"], np.zeros((n, 12))) and np.all(got["contact"] == 0) and np.all(got["gap"] > 9.0)
+    q0, v0 = d["q"].clone(), d["v"].clone()
+    solver.integrate(q0, v0, d["M"], d["h"], d["Jc"], d["tau"], torch.zeros_like(d["normals"]), d["tau_ext"])
+    torch.cuda.synchronize()
+    assert torch.equal(q, q0) and torch.equal(v, v0)
+
+
+BUMP_FOOT = {"G": "rl_foot", "P": "back_right_foot"}
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("which", ["G", "P"])
+def test_reordered_models_only_the_named_foot_responds(torch_cuda, hip_lib, tmp_path, which, n, dtype):
+    """Joint and foot order not leg-major, both scalar types, every parity size: all feet 1 cm above their ground but ONE, named, with a 1.5 cm bump
+    under it.  Only that foot's rows of f_gr and only its contact bit respond; the force equals the reference's, which reads the leg's joint columns
+    by the caller's indices; and the one-launch plant applies it to that leg (= ground_force -> integrate, = ground_ref).  fp32: the gates of the
+    parity tests (8 x ground_ref.F32_ERR; the integrator's 1e-4 against the reference)."""
+    torch = torch_cuda
+    spec = limit_models.specs(tmp_path)[which]
+    assert [j for js in spec.legs for j in js] != list(range(12))
+    b = spec.feet.index(BUMP_FOOT[which])
+    B = synth.make_batch(3, n, spec.total_mass, rank=120)
+    q, v = B["q"], 0.05 * B["v"]          # slow feet: the damping term cannot lift the bumped foot's force off the clamp
+    dyn = spec.oracle.dynamics(q, v)
+    P = R.params()
+    height = np.zeros((n, 4))
+    for k in range(4):
+        lever = R.foot_words(dyn["Jc"], v, k, spec.legs)[0]
+        pf = SR.foot_kin(spec.flat, k, q, v)["pf"]
+        assert np.abs(q[:, 0:3] + lever - pf).max() < 1e-12           # row k of the buffers is foot k of the caller's list
+        height[:, k] = pf[:, 2] - 0.01 + (0.015 if k == b else 0.0)
+    c = dict(q=q, v=v, normals=B["normals"], height=height, mu=B["mu"], tau=B["tau_prev"], tau_ext=np.zeros((n, 18)), dyn=dyn)
+    q_ref, v_ref, g = R.integrate_ground(P, DT, dyn, c["tau"], c["normals"], height, c["mu"], c["tau_ext"], q, v, spec.legs)
+    assert np.all(g["fn"][:, b] > P["f_touch"] * 1.5) and np.all(np.delete(g["gap"], b, 1) > 0)
+    # the own-leg columns matter: the joint velocities move the bumped foot's force by more than the fp32 gate
+    still = R.ground_force(P, q, np.concatenate([v[:, :6], np.zeros((n, 12))], 1), dyn["Jc"], c["normals"], height, c["mu"], spec.legs)
+    assert np.abs(still["f_gr"] - g["f_gr"]).max() > 10 * F32_GATE["f_gr"] * np.abs(g["f_gr"]).max()
+    solver = _solver(spec.model, dtype, max_batch=n)
+    d = _dev_case(torch, c, dtype)
+    got = _force(torch, solver, d, _outs(torch, n, dtype))
+    rows = [3 * b, 3 * b + 1, 3 * b + 2]
+    assert np.all(got["contact"] == 1 << b)
+    assert np.array_equal(np.delete(got["f_gr"], rows, 1), np.zeros((n, 9))) and np.all(got["f_gr"][:, 3 * b + 2] > 0)
+    _gate(got["f_gr"], g["f_gr"], dtype, "f_gr", n)
+    _gate(got["gap"], g["gap"], dtype, "gap", n)
+    q2, v2 = d["q"].clone(), d["v"].clone()
+    solver.integrate(q2, v2, d["M"], d["h"], d["Jc"], d["tau"], to_dev(got["f_gr"], torch, _td(torch, dtype)), d["tau_ext"])
+    one = _plant(torch, solver, d, _outs(torch, n, dtype), d["q"].clone(), d["v"].clone())
+    assert np.array_equal(one["contact"], got["contact"])
+    _gate(one["f_gr"], got["f_gr"].astype(np.float64), dtype, "f_gr", n)
+    _gate(one["q"], to_host(q2).astype(np.float64), dtype, "q", n)
+    _gate(one["v"], to_host(v2).astype(np.float64), dtype, "v", n)
+    tol = TIGHT64 if dtype == "f64" else F32_DYN
+    eq, ev = relerr(one["q"], q_ref), relerr(one["v"], v_ref)
+    print("reordered %s %s n=%d against ground_ref: q %.3g v %.3g" % (which, dtype, n, eq, ev))
+    assert eq < tol and ev < tol
+    # ... and the force reached the plant: without the bump the same call ends elsewhere, by more than the gate
+    free = R.integrate_ground(P, DT, dyn, c["tau"], c["normals"], height - np.where(np.arange(4) == b, 0.015, 0.0), c["mu"], c["tau_ext"], q, v,
+                              spec.legs)
+    assert relerr(free[1], v_ref) > 100 * tol
+
+
+def test_argument_checks_and_parameters(torch_cuda, gpu_model):
+    import ctypes as C
+    import wbc_quadruped_dob_amd as W
+    torch = torch_cuda
+    solver = _solver(gpu_model, "f64", max_batch=16)
+    L = W.lib()
+    z = lambda r, n=16: torch.zeros((r, n), dtype=torch.float64, device="cuda")
+    zi = lambda n=16: torch.zeros(n, dtype=torch.int32, device="cuda")
+    q = z(19); q[6] = 1.0; q[2] = 0.4
+    nrm = z(12); nrm[2::3] = 1.0
+    p = lambda t: C.c_void_p(t.data_ptr())
+    d = solver.dynamics(q, z(18), want=("M", "h", "Jc"))
+    # N = 0: WBC_OK without looking at the buffers
+    assert L.wbc_ground_force_batch(solver._h, 0, *([None] * 10)) == 0
+    assert L.wbc_integrate_ground_batch(solver._h, 0, *([None] * 14)) == 0
+    # each required pointer in turn; contact, gap (and tau_ext) may be NULL
+    keep = dict(v=z(18), height=z(4), mu=z(4) + 0.5, f_gr=z(12), tau=z(12), q2=q.clone())      # alive while their addresses are in use
+    full = [p(q), p(keep["v"]), p(d["Jc"]), p(nrm), p(keep["height"]), p(keep["mu"]), p(keep["f_gr"]), None, None]
+    assert L.wbc_ground_force_batch(solver._h, 16, *full, None) == 0
+    for i in range(7):
+        a = list(full); a[i] = None
+        assert L.wbc_ground_force_batch(solver._h, 16, *a, None) == 1, i
+    assert L.wbc_ground_force_batch(None, 16, *full, None) == 1
+    full = [p(keep["q2"]), p(keep["v"]), p(d["M"]), p(d["h"]), p(d["Jc"]), p(keep["tau"]), p(nrm), p(keep["height"]), p(keep["mu"]), None,
+            p(keep["f_gr"]), None, None]
+    assert L.wbc_integrate_ground_batch(solver._h, 16, *full, None) == 0
+    for i in (0, 1, 2, 3, 4, 5, 6, 7, 8, 10):
+        a = list(full); a[i] = None
+        assert L.wbc_integrate_ground_batch(solver._h, 16, *a, None) == 1, i
+    assert L.wbc_integrate_ground_batch(None, 16, *full, None) == 1
+    # N > max_batch
+    for call in (lambda: solver.ground_force(z(19, 17), z(18, 17), z(216, 17), z(12, 17), z(4, 17), z(4, 17)),
+                 lambda: solver.integrate_ground(z(19, 17), z(18, 17), z(171, 17), z(18, 17), z(216, 17), z(12, 17), z(12, 17), z(4, 17), z(4, 17))):
+        with pytest.raises(W.WbcError) as e:
+            call()
+        assert e.value.code == 7   # WBC_E_CAPACITY
+    # invalid and non-finite parameters; a struct of a smaller build; a valid set is taken
+    for bad in (dict(k_n=-1.0), dict(c_n=-0.1), dict(c_t=-1e-9), dict(f_touch=-1.0), dict(k_n=float("nan")), dict(c_n=float("inf")),
+                dict(c_t=float("nan")), dict(f_touch=float("inf"))):
+        with pytest.raises(W.WbcError):
+            solver.set_ground_params(bad)
+    small = W.GroundParams.default(); small.struct_size = 8
+    assert L.wbc_solver_set_ground_params(solver._h, C.byref(small)) == 1
+    assert W.GroundParams.default().as_dict() == R.DEFAULT_PARAMS
+    solver.set_ground_params(dict(k_n=0.0, c_n=0.0, c_t=0.0, f_touch=0.0))
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_set_ground_params_reaches_the_kernel(torch_cuda, gpu_model, dtype):
+    """A robot at rest 4 mm in flat ground: f_n = k_n |gap|, so doubling k_n doubles it (to rounding), and f_touch decides the bit.  Tolerances: the
+    gap is the difference of two heights below 0.5 m formed on the device, so 8 roundings of 0.5 m in the scalar type (fp64: 1e-12, a looser round
+    number); f_n inherits k_n times that; doubling k_n is exact in binary, so f_b - 2 f_a is held to 8 roundings of f_a."""
+    torch = torch_cuda
+    n = 15
+    B = synth.make_batch(3, n, gpu_model.total_mass, rank=121)
+    td = _td(torch, dtype)
+    eps = float(np.finfo(np.float64 if dtype == "f64" else np.float32).eps)
+    tol_gap = 1e-12 if dtype == "f64" else 8 * eps * 0.5
+    solver = _solver(gpu_model, dtype, max_batch=n)
+    q, v = to_dev(B["q"], torch, td), torch.zeros((18, n), dtype=td, device="cuda")
+    d = solver.dynamics(q, v, want=("M", "h", "Jc", "pf"))
+    assert float(d["pf"].reshape(4, 3, n)[:, 2, :].abs().max()) < 0.5
+    height = (d["pf"].reshape(4, 3, n)[:, 2, :] + 4e-3).contiguous()
+    args = (q, v, d["Jc"], to_dev(B["normals"], torch, td), height, to_dev(B["mu"], torch, td))
+    a = solver.ground_force(*args, want_gap=True)
+    solver.set_ground_params(dict(k_n=2 * R.DEFAULT_PARAMS["k_n"], f_touch=200.0))
+    b = solver.ground_force(*args)
+    torch.cuda.synchronize()
+    fa, fb, gap = (to_host(x).astype(np.float64) for x in (a["f_gr"], b["f_gr"], a["gap"]))
+    k_n = R.DEFAULT_PARAMS["k_n"]
+    print("set_ground_params %s: gap error %.3g (tol %.3g), f_n error %.3g, doubling error %.3g" %
+          (dtype, np.abs(gap + 4e-3).max(), tol_gap, np.abs(fa[:, 2::3] - k_n * 4e-3).max(), np.abs(fb - 2 * fa).max()))
+    assert np.abs(gap + 4e-3).max() < tol_gap
+    assert np.abs(fa[:, 2::3] - k_n * 4e-3).max() < max(1e-9, k_n * tol_gap) and np.abs(fb - 2 * fa).max() < max(1e-9, 8 * eps * np.abs(fa).max())
+    assert np.all(a["contact"].cpu().numpy() == 15) and np.all(b["contact"].cpu().numpy() == 0)      # 80 N > 5 N; 160 N < 200 N
+
+
+# ---- the four-call tick: gait(contact = last tick's) -> reference_swing -> step -> integrate_ground
+def _walk_solver(model, flat, n):
+    return _solver(model, "f64", max_batch=n, dt=GR.DYADIC_DT, ref_params=SR.loop_ref_params(), gait=GR.walk_params(flat), swing=GR.WALK_SWING_PARAMS)
+
+
+def _walk_dev(torch, case):
+    td = torch.float64
+    d = {k: to_dev(case[k], torch, td) for k in ("cmd", "plan", "normals", "mu", "height0", "height1")}
+    n = case["q"].shape[0]
+    e = lambda r: torch.zeros((r, n), dtype=td, device="cuda")
+    i = lambda: torch.zeros(n, dtype=torch.int32, device="cuda")
+    d["ref"] = dict(w_des=e(6), vdot_des=e(18))
+    d["tick"] = dict(tau=e(12), f=e(12), status=i(), iters=i(), M=e(171), h=e(18), Jc=e(216), pf=e(12))
+    d["events"], d["f_gr"], d["height"] = i(), e(12), d["height0"].clone()
+    return d
+
+
+def _walk_state(torch, case):
+    td = torch.float64
+    return dict(q=to_dev(case["q"], torch, td), v=to_dev(case["v"], torch, td), phase=torch.from_numpy(case["phase"]).to(td).cuda(),
+                mask=torch.from_numpy(case["mask"]).to(torch.int32).cuda(), swing=to_dev(case["swing"], torch, td),
+                contact=torch.zeros(case["q"].shape[0], dtype=torch.int32, device="cuda"))
+
+
+def _tick(solver, d, st):
+    """One walking tick on the state st (q, v, phase, mask, swing, contact advance in place); no host work between the four launches"""
+    solver.gait(st["q"], st["v"], d["cmd"], st["phase"], st["mask"], st["swing"], contact=st["contact"], events=d["events"])
+    solver.reference_swing(st["q"], st["v"], d["plan"], st["mask"], st["swing"], 0.0, out=d["ref"])
+    solver.step(st["q"], st["v"], d["ref"]["w_des"], d["ref"]["vdot_des"], d["normals"], d["mu"], st["mask"], out=d["tick"], want_mats=True)
+    solver.integrate_ground(st["q"], st["v"], d["tick"]["M"], d["tick"]["h"], d["tick"]["Jc"], d["tick"]["tau"], d["normals"], d["height"], d["mu"],
+                            f_gr=d["f_gr"], contact=st["contact"])
+
+
+def test_captured_four_call_tick_replays_bit_for_bit(torch_cuda, gpu_model, flat_model, oracle):
+    """gait -> reference_swing -> step -> integrate_ground at N = 17, captured once: three replays from the same start = three eager ticks, bit for
+    bit -- the pattern of tests/test_gpu_gait.py.  The ground lies 1 mm above the feet's starting height, so the plant pushes from the first tick."""
+    torch = torch_cuda
+    n = 17
+    case = R.walk_case(flat_model, oracle, n)
+    solver = _walk_solver(gpu_model, flat_model, n)
+    d = _walk_dev(torch, case)
+    d["height"] += 1e-3
+    start = _walk_state(torch, case)
+    st = {k: x.clone() for k, x in start.items()}
+    for _ in range(3):
+        _tick(solver, d, st)
+    torch.cuda.synchronize()
+    assert torch.all(st["mask"] == 0b1001) and bool((st["contact"] != 0).all())
+    eager = {k: x.clone() for k, x in st.items()}
+    eager["f_gr"] = d["f_gr"].clone()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):   # warm-up on the side stream (torch's capture recipe)
+        _tick(solver, d, {k: x.clone() for k, x in start.items()})
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    for k in st:
+        st[k].copy_(start[k])
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        _tick(solver, d, st)
+    solver.set_ground_params(dict(k_n=1.0, c_n=0.0, c_t=0.0))   # a captured graph keeps the law it was captured with
+    for k in st:
+        st[k].copy_(start[k])
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    for k in st:
+        assert torch.equal(st[k], eager[k]), k
+    assert torch.equal(d["f_gr"], eager["f_gr"]) and bool((d["f_gr"] != 0).any())
+    assert not torch.equal(st["q"], start["q"])
+
+
+def test_closed_loop_matches_the_cpu_loop(torch_cuda, gpu_model, flat_model, oracle):
+    """The loop of tests/test_ground_oracle.py on the device, 16 robots, fp64, 512 ticks, the terrain changing under the marked feet at tick 64 (a
+    copy on the stream): mask, events and contact of every tick equal the CPU loop's exactly, every status is 0, the early touchdowns fall on the same
+    ticks, and end-of-loop q, v agree within max(1e-6, 10 A 1e-9) of the largest entry = 1e-6: the CPU loop amplifies a perturbation of the start by
+    A = 2.3 (ground_ref.WALK_AMPLIFICATION = 5 is its bound), so 10 A 1e-9 = 5e-8 stays below the floor."""
+    torch = torch_cuda
+    n, ticks = 16, R.WALK_TICKS
+    case, cpu = R.cpu_walk(flat_model, oracle, n)
+    assert cpu["status_ok"] and len(cpu["early"]) >= 1
+    gate = max(1e-6, 10 * R.WALK_AMPLIFICATION * 1e-9)
+    assert gate <= 1e-3
+    solver = _walk_solver(gpu_model, flat_model, n)
+    d = _walk_dev(torch, case)
+    st = _walk_state(torch, case)
+    rec = {k: torch.zeros((ticks, n), dtype=torch.int32, device="cuda") for k in ("mask", "events", "contact", "status")}
+    phases = torch.zeros((ticks, n), dtype=torch.float64, device="cuda")
+    for k in range(ticks):
+        d["plan"][7] = k * GR.DYADIC_DT                   # the CoM plan's elapsed time (a fill on the stream, no synchronisation)
+        if k == R.BUMP_TICK:
+            d["height"].copy_(d["height1"])
+        _tick(solver, d, st)
+        rec["mask"][k].copy_(st["mask"]); rec["events"][k].copy_(d["events"]); rec["contact"][k].copy_(st["contact"])
+        rec["status"][k].copy_(d["tick"]["status"]); phases[k].copy_(st["phase"])
+    torch.cuda.synchronize()
+    rec = {k: x.cpu().numpy() for k, x in rec.items()}
+    assert np.all(rec["status"] == 0)
+    assert np.array_equal(rec["mask"], cpu["masks"]) and np.array_equal(rec["events"], cpu["events"]) and np.array_equal(rec["contact"], cpu["contacts"])
+    early = R.early_touchdowns(GR.walk_params(flat_model), phases.cpu().numpy(), rec["events"])
+    assert early == cpu["early"]
+    eq, ev = relerr(to_host(st["q"]), cpu["q"]), relerr(to_host(st["v"]), cpu["v"])
+    print("walking loop on the ground plant: q %.3g v %.3g (gate %.3g); %d early touchdowns" % (eq, ev, gate, len(early)))
+    assert eq < gate and ev < gate

@@ -264,6 +264,13 @@ def lib():
             L.wbc_solver_set_gait_params.argtypes = [C.c_void_p, C.c_void_p]
             L.wbc_gait_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
             L.wbc_compute_gait.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4
+        # ground-contact plant: additive to ABI 10, detected by the symbols in the same way (_ground_lib)
+        if hasattr(L, "wbc_integrate_ground_batch"):
+            L.wbc_ground_params_default.argtypes = [C.c_void_p]
+            L.wbc_ground_params_default.restype = None
+            L.wbc_solver_set_ground_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_ground_force_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 10
+            L.wbc_integrate_ground_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 14
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -306,6 +313,14 @@ def _gait_lib():
     L = lib()
     if not hasattr(L, "wbc_gait_batch"):
         raise RuntimeError("%s lacks the gait-scheduler entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+def _ground_lib():
+    """lib(), for the ground plant's calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_integrate_ground_batch"):
+        raise RuntimeError("%s lacks the ground-plant entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     return L
 
 
@@ -384,6 +399,30 @@ class SwingParams(C.Structure):
             else:
                 raise KeyError("SwingParams has no field %r" % k)
         return p
+
+
+class GroundParams(C.Structure):
+    """wbc_ground_params: the contact law of the ground plant (include/wbc_hip.h, "Ground-contact plant")"""
+    _fields_ = [("struct_size", C.c_size_t), ("k_n", C.c_double), ("c_n", C.c_double), ("c_t", C.c_double), ("f_touch", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = GroundParams()
+        _ground_lib().wbc_ground_params_default(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d):
+        """keys k_n, c_n, c_t, f_touch; missing keys keep the defaults"""
+        p = GroundParams.default()
+        for k, val in d.items():
+            if k not in ("k_n", "c_n", "c_t", "f_touch"):
+                raise KeyError("GroundParams has no field %r" % k)
+            setattr(p, k, float(val))
+        return p
+
+    def as_dict(self):
+        return dict(k_n=self.k_n, c_n=self.c_n, c_t=self.c_t, f_touch=self.f_touch)
 
 
 GAIT_CMD_WORDS = 4   # include/wbc_hip.h: WBC_GAIT_CMD_WORDS -- cmd [GAIT_CMD_WORDS, N]: vx, vy (heading frame), wz, z_g
@@ -935,6 +974,50 @@ class Solver:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _check(_gait_lib().wbc_compute_gait(self._h, p(q), p(v), p(cmd), int(contact), C.byref(ph), C.byref(mk), p(sw), C.byref(ev)), "wbc_compute_gait")
         return ph.value, mk.value, sw, ev.value
+
+    def set_ground_params(self, p):
+        """p: GroundParams or dict (see GroundParams.from_dict): the contact law of every later ground call of this solver."""
+        if isinstance(p, dict):
+            p = GroundParams.from_dict(p)
+        _check(_ground_lib().wbc_solver_set_ground_params(self._h, C.byref(p)), "wbc_solver_set_ground_params")
+
+    def _ground_out(self, N, f_gr, contact, gap, want_contact, want_gap, device):
+        torch = self.torch
+        f_gr = self.empty(3 * self.model.nf, N) if f_gr is None else f_gr
+        if contact is None and want_contact:
+            contact = torch.empty(N, dtype=torch.int32, device=device)
+        if gap is None and want_gap:
+            gap = self.empty(self.model.nf, N)
+        return f_gr, contact, gap
+
+    def ground_force(self, q, v, Jc, normals, height, mu, f_gr=None, contact=None, gap=None, want_contact=True, want_gap=False):
+        """The contact law alone (wbc_ground_force_batch): the terrain n_k . x = height[k] under every foot pushes back with f_gr [12, N]; contact [N]
+        int32 has bit k set where foot k presses harder than f_touch; gap [4, N] is the signed distance (negative = penetration).  Tensors not
+        passed are allocated.  Returns dict(f_gr, contact, gap)."""
+        m = self.model
+        N = q.shape[1]
+        f_gr, contact, gap = self._ground_out(N, f_gr, contact, gap, want_contact, want_gap, q.device)
+        _check(_ground_lib().wbc_ground_force_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(Jc, 3 * m.nf * m.nv, N),
+                                                    self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N),
+                                                    self._ptr(f_gr, 3 * m.nf, N), self._ptr(contact, 1, N, self.torch.int32),
+                                                    self._ptr(gap, m.nf, N), self._stream()), "wbc_ground_force_batch")
+        return dict(f_gr=f_gr, contact=contact, gap=gap)
+
+    def integrate_ground(self, q, v, M, h, Jc, tau, normals, height, mu, tau_ext=None, f_gr=None, contact=None, gap=None, want_contact=True,
+                         want_gap=False):
+        """ground_force() followed by integrate(f = f_gr), as one launch (wbc_integrate_ground_batch): q, v advance IN PLACE (one dt) under the
+        terrain's reaction forces instead of the planned ones.  Returns dict(f_gr, contact, gap); pass contact to the next tick's gait()."""
+        m = self.model
+        N = q.shape[1]
+        f_gr, contact, gap = self._ground_out(N, f_gr, contact, gap, want_contact, want_gap, q.device)
+        _check(_ground_lib().wbc_integrate_ground_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
+                                                        self._ptr(M, m.nv * (m.nv + 1) // 2, N), self._ptr(h, m.nv, N),
+                                                        self._ptr(Jc, 3 * m.nf * m.nv, N), self._ptr(tau, m.nj, N),
+                                                        self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N),
+                                                        self._ptr(tau_ext, m.nv, N), self._ptr(f_gr, 3 * m.nf, N),
+                                                        self._ptr(contact, 1, N, self.torch.int32), self._ptr(gap, m.nf, N), self._stream()),
+               "wbc_integrate_ground_batch")
+        return dict(f_gr=f_gr, contact=contact, gap=gap)
 
     def rollout_tracking(self, horizon, q, v, plan, normals, mu, mask, out, w_des, vdot_des, obs_integ=None, obs_r=None,
                          tau_ext=None, tau_traj=None, com_traj=None, payload=None):

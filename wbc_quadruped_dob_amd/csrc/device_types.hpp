@@ -224,6 +224,24 @@ template <class T> struct GaitArgs {
   DevGaitParams<T> P;
 };
 
+// ground-contact plant (ground.hip.hpp): the contact law's constants and what a call reads and writes -- kernel arguments BY VALUE like the gait schedule
+// (wbc_solver_set_ground_params only fills the solver's host copy)
+template <class T> struct DevGroundParams { T k_n, c_n, c_t, f_touch; };
+template <class T> struct GroundIO {
+  const T* normals; const T* height; const T* mu;   // [12][N], [4][N], [4][N]
+  T* f_gr;        // [12][N]
+  int* contact;   // [N] or null
+  T* gap;         // [4][N] or null
+  DevGroundParams<T> P;
+};
+template <class T> struct GroundArgs {   // ground_force_kernel
+  size_t N;
+  const T* q; const T* v; const T* Jc;
+  unsigned long long jpack;   // see SweepArgs::jpack
+  GroundIO<T> g;
+};
+template <class T> struct GroundIntegrateArgs : IntegrateArgs<T> { GroundIO<T> g; };   // ground_integrate_kernel (IntegrateArgs::f is not read)
+
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc
 constexpr int SW_STEP = 2;  // write the step workspace (d, b, taup, JcL)

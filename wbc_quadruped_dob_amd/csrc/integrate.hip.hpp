@@ -106,12 +106,15 @@ constexpr int INT_FACT_WORDS = 27;
 // not kept (-DWBC_RO_EARLY_BARRIER=1).
 // PAYLOAD (plant model mismatch, `payload` = [PAYLOAD_WORDS][N]): phase 1 adds dM_bb to the base block (with HAND: one more body in the composite
 // (m, R h, R I R^T) before the block is rebuilt), phase 2 subtracts dh_b from the base right-hand side.  false: the code of rounds 1-6, unchanged.
+// GROUND (ground-contact plant, ground.hip.hpp): this lane's foot force is `fground`, a register value the caller has just computed from the contact law,
+// instead of rows 3 leg .. 3 leg + 2 of a.f, which is not read.  false: the code as it was.
 template <class T, int SPW = 16, class Between = IntegrateNoWait, int PHASE = 0, bool UNGUARD = false, bool HAND = false, bool RESI = false,
-          class AfterState = IntegrateNoWait, bool SIMG_ = false, bool PAYLOAD = false, bool SCORE = false>
+          class AfterState = IntegrateNoWait, bool SIMG_ = false, bool PAYLOAD = false, bool SCORE = false, bool GROUND = false>
 WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const IntegrateArgs<T>& a, Between between = Between(), const T* hand_ = nullptr,
                             const T* res_ = nullptr, T* fact = nullptr, AfterState after_state = AfterState(), const T* payload = nullptr,
-                            const ScoreTick<T>* sc = nullptr) {
+                            const ScoreTick<T>* sc = nullptr, V3<T> fground = V3<T>()) {
   static_assert(PHASE == 0 || PHASE == 1 || PHASE == 2, "phase");
+  static_assert(!GROUND || (PHASE == 0 && !RESI), "the ground plant is the stand-alone kernel");
   static_assert(!SCORE || (PHASE == 2 && RESI && SIMG_), "the cost is accumulated in phase 2 of the persistent rollout");
   static_assert(PHASE == 0 || HAND, "the split phases hand M's blocks over in LDS");
   constexpr bool FASTR = PHASE != 0 && SIMG_;   // (rollout workgroups with the state image) rsqrt_fast, see dyn_sweep.hip.hpp
@@ -332,8 +335,9 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
 
   // ================================================================== phase 2: tau, f, h, q, v
   // ---- my leg: rhs_l = tau_l + JcL^T f_l + tau_ext_l - h_l
-  const V3<T> fl = RESI ? mk<T>(rs[(12 + 3 * leg + 0) * 16], rs[(12 + 3 * leg + 1) * 16], rs[(12 + 3 * leg + 2) * 16])
-                      : mk<T>(LDL(a.f, 0, 3), LDL(a.f, 1, 3), LDL(a.f, 2, 3));
+  const V3<T> fl = GROUND ? fground
+                 : RESI ? mk<T>(rs[(12 + 3 * leg + 0) * 16], rs[(12 + 3 * leg + 1) * 16], rs[(12 + 3 * leg + 2) * 16])
+                        : mk<T>(LDL(a.f, 0, 3), LDL(a.f, 1, 3), LDL(a.f, 2, 3));
   T rl[3], taul[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {

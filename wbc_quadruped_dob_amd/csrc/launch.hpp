@@ -134,5 +134,9 @@ template <class T> hipError_t k_swing_reference(const LaunchCtx& L, const DevMod
 template <class T> hipError_t k_reference_swing(const LaunchCtx& L, const DevModel<T>* model, const DevRefParams<T>* G, const RefArgs<T>& a, const SwingArgs<T>& sa);
 // gait scheduler (gait.hip.hpp): gait_kernel<T> advances phase, rewrites mask and the lifted feet's plan words of swing, in place
 template <class T> hipError_t k_gait(const LaunchCtx& L, const DevModel<T>* model, const GaitArgs<T>& a);
+// ground-contact plant (ground.hip.hpp): ground_force_kernel<T> is the contact law alone (f_gr, contact, gap from q, v, Jc and the terrain);
+// ground_integrate_kernel<T> is the same law followed by k_integrate with f = f_gr handed over in registers -- one launch
+template <class T> hipError_t k_ground_force(const LaunchCtx& L, const DevModel<T>* model, const GroundArgs<T>& a);
+template <class T> hipError_t k_ground_integrate(const LaunchCtx& L, const DevModel<T>* model, const GroundIntegrateArgs<T>& a);
 
 }  // namespace wbc

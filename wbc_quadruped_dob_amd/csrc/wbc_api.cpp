@@ -94,6 +94,7 @@ struct wbc_solver {
   wbc_score_params score;    // the weights of the scored rollouts (wbc_solver_set_score_params; kernel arguments by value), defaults at creation
   wbc_swing_params swing;    // the gains of the swing-foot references (wbc_solver_set_swing_params; kernel arguments by value), defaults at creation
   void* d_swing_one = nullptr;   // wbc_compute_swing_reference's staging: SWING_ONE_SCALARS scalars + the mask
+  wbc_ground_params ground;  // the contact law of the ground plant (wbc_solver_set_ground_params; kernel arguments by value), the defaults at creation
   wbc_gait_params gait;      // the schedule of the gait scheduler (wbc_solver_set_gait_params; kernel arguments by value), the model's defaults at creation
   void* d_gait_one = nullptr;    // wbc_compute_gait's staging: GAIT_ONE_SCALARS scalars + contact, mask, events
   // torque-limit post-pass (wbc_limit_torques_batch): the limits travel as a kernel argument like the score weights
@@ -673,6 +674,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   wbc_score_params_default(&s->score);
   wbc_swing_params_default(&s->swing);
   wbc_gait_params_default(m, &s->gait);
+  wbc_ground_params_default(&s->ground);
   for (int j = 0; j < WBC_MAXV; ++j) s->model_effort[j] = (j < m->fm.nj() && j < (int)m->fm.effort_limit.size()) ? m->fm.effort_limit[j] : HUGE_VAL;
   std::memcpy(s->tau_max, s->model_effort, sizeof(s->tau_max));
   s->limit_grid = limit_qp_grid(prop.multiProcessorCount);
@@ -1589,6 +1591,82 @@ extern "C" int wbc_gait_batch(wbc_solver* s, size_t N, const void* q, const void
   hipStream_t st = (hipStream_t)stream;
   return s->dtype == WBC_F64 ? gait_impl<double>(s, N, q, v, cmd, contact, phase, mask, swing, events, st)
                              : gait_impl<float>(s, N, q, v, cmd, contact, phase, mask, swing, events, st);
+}
+
+// ---- ground-contact plant: the contact law's constants, the law alone, the law + forward dynamics as one launch
+extern "C" void wbc_ground_params_default(wbc_ground_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->k_n = 2e4; p->c_n = 150.0; p->c_t = 200.0; p->f_touch = 5.0;   // how they were fixed: include/wbc_hip.h
+}
+
+extern "C" int wbc_solver_set_ground_params(wbc_solver* s, const wbc_ground_params* p) {
+  if (!s || !p) return fail(WBC_E_INVALID, "null argument");
+  if (p->struct_size < sizeof(wbc_ground_params)) return fail(WBC_E_INVALID, "wbc_ground_params: struct_size too small (call wbc_ground_params_default first)");
+  const double val[4] = {p->k_n, p->c_n, p->c_t, p->f_touch};
+  for (int i = 0; i < 4; ++i)
+    if (!(val[i] >= 0) || !std::isfinite(val[i])) return fail(WBC_E_INVALID, "wbc_ground_params: k_n, c_n, c_t, f_touch must be finite and >= 0");
+  s->ground = *p;
+  return WBC_OK;
+}
+
+template <class T>
+static void ground_io(GroundIO<T>& g, const wbc_solver* s, const void* normals, const void* height, const void* mu, void* f_gr, int* contact, void* gap) {
+  g.normals = (const T*)normals; g.height = (const T*)height; g.mu = (const T*)mu;
+  g.f_gr = (T*)f_gr; g.contact = contact; g.gap = (T*)gap;
+  g.P.k_n = (T)s->ground.k_n; g.P.c_n = (T)s->ground.c_n; g.P.c_t = (T)s->ground.c_t; g.P.f_touch = (T)s->ground.f_touch;
+}
+
+template <class T>
+static int ground_force_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height,
+                             const void* mu, void* f_gr, int* contact, void* gap, hipStream_t st) {
+  GroundArgs<T> a;
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.Jc = (const T*)Jc; a.jpack = s->jpack;
+  ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
+  LaunchCtx L; L.st = st;
+  hipError_t e = k_ground_force<T>(L, dev_model<T>(s), a);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("ground force launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
+extern "C" int wbc_ground_force_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height,
+                                      const void* mu, void* f_gr, int* contact, void* gap, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !Jc || !normals || !height || !mu || !f_gr) return fail(WBC_E_INVALID, "null argument");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64 ? ground_force_impl<double>(s, N, q, v, Jc, normals, height, mu, f_gr, contact, gap, st)
+                             : ground_force_impl<float>(s, N, q, v, Jc, normals, height, mu, f_gr, contact, gap, st);
+}
+
+template <class T>
+static int integrate_ground_impl(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
+                                 const void* normals, const void* height, const void* mu, const void* tau_ext, void* f_gr, int* contact, void* gap,
+                                 hipStream_t st) {
+  GroundIntegrateArgs<T> a;
+  integrate_args<T>(a, s, N, q, v, M, h, Jc, tau, nullptr, tau_ext, nullptr);   // (zeroes the IntegrateArgs part; f is not read)
+  ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
+  LaunchCtx L; L.st = st;
+  hipError_t e = k_ground_integrate<T>(L, dev_model<T>(s), a);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("integrate ground launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
+extern "C" int wbc_integrate_ground_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
+                                          const void* normals, const void* height, const void* mu, const void* tau_ext, void* f_gr, int* contact,
+                                          void* gap, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !M || !h || !Jc || !tau || !normals || !height || !mu || !f_gr) return fail(WBC_E_INVALID, "null argument");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64 ? integrate_ground_impl<double>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, f_gr, contact, gap, st)
+                             : integrate_ground_impl<float>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, f_gr, contact, gap, st);
 }
 
 // ---- scored rollouts: the weights, the superset rollout, one tick's cost, the per-group selection
