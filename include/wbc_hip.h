@@ -206,6 +206,12 @@ int wbc_dispatch_thresholds(int dtype, int observer_order, const wbc_solver_opti
 /* diagnostics (synchronises the device): states of the last two-kernel tick that the per-lane QP kernel handed to the dense one */
 int wbc_solver_qp_handover(wbc_solver* s, int* count);
 void wbc_solver_destroy(wbc_solver* s);
+/* Replaces the solver's parameters (checked as at creation; a rejected set changes nothing).  Every field is RUN-TIME data: the batch calls read the
+ * parameters when they are ENQUEUED and pass them to their kernels as arguments, so every call made after this one -- ticks, rollouts, the gait
+ * scheduler's control period -- runs under the new values, bit-identical to a solver created with them; work already enqueued keeps the old ones.
+ * Nothing is captured by argument structs a caller prepared earlier (the Python binding's Solver.prepare_step closure follows the solver).  A
+ * hipGraph CAPTURED before the call keeps the parameters it was captured with: re-capture after changing them.  observer_order may change; a tick
+ * under an order > 0 needs the observer state buffers.  Not inside a stream capture; not concurrently with a call on the same solver. */
 int wbc_solver_set_params(wbc_solver* s, const wbc_params* p);
 
 typedef struct wbc_batch_in {
@@ -655,7 +661,7 @@ wbc_solver* wbc_multi_solver(wbc_multi* mm, int shard);     /* the shard's solve
  * event recorded on this stream). */
 void* wbc_multi_stream(wbc_multi* mm, int shard);
 int wbc_multi_rccl_ranks(const wbc_multi* mm);              /* ranks of the RCCL communicator; 0 when RCCL is not in use */
-int wbc_multi_set_params(wbc_multi* mm, const wbc_params* p);
+int wbc_multi_set_params(wbc_multi* mm, const wbc_params* p);   /* wbc_solver_set_params on every shard: checked once, then applied to all */
 /* One control tick of n_total states.  in[k] / out[k] / obs[k] (arrays of wbc_multi_size entries; obs may be NULL when
  * the observer is off) describe shard k's slice: device pointers on devices[k], component-major with N = the shard's
  * count.  Enqueues every shard on its stream and returns without synchronising. */

@@ -19,6 +19,8 @@ namespace wbc {
 // SWING (swing_ref.hip.hpp, wbc_reference_swing_batch): a functor that replaces the posture law of the lane's leg where the leg swings, from what this body
 // holds in registers anyway (R, E, the base rows of vdot_des).  RefNoSwing (every kernel but com_swing_reference_kernel): no call, no code.
 struct RefNoSwing { static constexpr bool on = false; };
+WBC_DEV double fma_w(double a, double b, double c) { return __builtin_fma(a, b, c); }
+WBC_DEV float fma_w(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 // EXT (persistent rollout kernel, fused_tick.hip.hpp): one wavefront of a larger workgroup, tables already in LDS.
 template <class T, bool EXT, int SPW = 16, bool SIMG = false, class SWING = RefNoSwing>   // SIMG: role of a rollout workgroup that keeps states / plans / references in LDS
 WBC_DEV void com_reference_body(const DevModel<T>* __restrict__ model, const DevRefParams<T>* __restrict__ G, const RefArgs<T>& a,
@@ -88,7 +90,23 @@ WBC_DEV void com_reference_body(const DevModel<T>* __restrict__ model, const Dev
     const V3<T> r = mk<T>(RCS(o + 27), RCS(o + 28), RCS(o + 29));
     const V3<T> ax = mk<T>(RCS(o + 30), RCS(o + 31), RCS(o + 32));
     const V3<T> h = mk<T>(RCS(o + 34), RCS(o + 35), RCS(o + 36));
-    const V3<T> om = tmul(E[k], omp) + ax * vl[k];
+    // E^T omp + ax qdot with every fused multiply-add WRITTEN: left to the compiler, com_reference_kernel and com_swing_reference_kernel contracted this
+    // sum differently, and with joint axes off the coordinate axes (ax qdot no longer exact) the fused call's w_des, com and base rows lost the
+    // bit-identity with wbc_reference_batch that include/wbc_hip.h promises (tests/test_gpu_variants.py)
+    // The stand-alone kernels only.  The rollout kernels' planner role (EXT) keeps the compiler's form and its register budget, so it may round om
+    // differently from com_reference_kernel by one unit in the last place: no contract ties the two bit for bit (the persistent tracking rollout is
+    // compared with per-tick launches to rounding).  Every OTHER expression of this body still relies on the compiler contracting both stand-alone
+    // instantiations alike; tests/test_gpu_variants.py asserts the bits on oblique, asymmetric and combined models at 17 ... 258 states.
+    V3<T> om;
+    if constexpr (EXT) {
+      om = tmul(E[k], omp) + ax * vl[k];
+    } else {
+#pragma clang fp contract(off)
+      const M3<T>& e = E[k];
+      om = mk<T>(fma_w(ax.x, vl[k], fma_w(e.a[6], omp.z, fma_w(e.a[0], omp.x, e.a[3] * omp.y))),
+                 fma_w(ax.y, vl[k], fma_w(e.a[7], omp.z, fma_w(e.a[1], omp.x, e.a[4] * omp.y))),
+                 fma_w(ax.z, vl[k], fma_w(e.a[8], omp.z, fma_w(e.a[2], omp.x, e.a[5] * omp.y))));
+    }
     const V3<T> vv = tmul(E[k], vp + cross(omp, r));
     pk[k] = vv * RCS(o + 33) + cross(om, h);
     omp = om; vp = vv;
