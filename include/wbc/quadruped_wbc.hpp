@@ -214,6 +214,23 @@ class QuadrupedWBC {
           "wbc_integrate_ground_batch");
   }
 
+  // Stiction on the ground plant (wbc_hip.h, "Stiction on the ground plant"): the ground calls with a per-foot anchor spring.  anchor [12][N] and
+  // stick [N] are the caller's device buffers and advance in place; the caller stores 0 into stick before the first tick.
+  // stictionParamsDefault(): k_t 2e4.
+  static wbc_stiction_params stictionParamsDefault() { wbc_stiction_params p; wbc_stiction_params_default(&p); return p; }
+  void setStictionParams(const wbc_stiction_params& p) { check(wbc_solver_set_stiction_params(solver_, &p), "wbc_solver_set_stiction_params"); }
+  void groundStickForce(size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height, const void* mu,
+                        void* anchor, int* stick, void* f_gr, int* contact = nullptr, void* gap = nullptr, void* stream = nullptr) {
+    check(wbc_ground_stick_force_batch(solver_, N, q, v, Jc, normals, height, mu, anchor, stick, f_gr, contact, gap, stream),
+          "wbc_ground_stick_force_batch");
+  }
+  void integrateGroundStick(size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau, const void* normals,
+                            const void* height, const void* mu, const void* tau_ext, void* anchor, int* stick, void* f_gr, int* contact = nullptr,
+                            void* gap = nullptr, void* stream = nullptr) {   // (the argument order of the C call)
+    check(wbc_integrate_ground_stick_batch(solver_, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, anchor, stick, f_gr, contact, gap, stream),
+          "wbc_integrate_ground_stick_batch");
+  }
+
   // Joint torque limits (wbc_hip.h, "Joint torque limits behind a tick").  effortLimits(): the URDF's <limit effort> per joint in jointNames() order,
   // HUGE_VAL where it gives none.  setTorqueLimits(): the limits the post-pass enforces (one value > 0 per joint; empty = back to the URDF's).
   std::vector<double> effortLimits() const {

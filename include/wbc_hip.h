@@ -573,11 +573,12 @@ int wbc_compute_gait(wbc_solver* s, const double* q, const double* v, const doub
  * toggles afterwards.  (k_n 2e4, c_n 200, c_t 500 did not pass: that eigenvalue was 2.03 and the foot forces alternated from tick to tick for good;
  * with the defaults it is 0.97.  tests/test_ground_oracle.py holds the measured settling time, residuals and stability ratios.)  A caller with another
  * dt or a lighter leg scales c_n, c_t with m_eff / dt.
- * Known limitation: viscous friction has no stiction -- a foot under a tangential load F creeps at F / c_t.
+ * Viscous friction has no stiction -- a foot under a tangential load F creeps at F / c_t under THESE calls; wbc_ground_stick_force_batch /
+ * wbc_integrate_ground_stick_batch ("Stiction" below) add a per-foot anchor spring that holds it.
  * Stream rules as for wbc_gait_batch: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at the buffers; a NULL
  * required pointer: WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
- * Out of scope: the payload plant (wbc_integrate_plant_batch); the rollout kernels and wbc_rollout_*; wbc_multi_*; stiction (a stateful anchor spring);
- * late touchdown in the gait rule; terrain-normal footholds. */
+ * Out of scope: the payload plant (wbc_integrate_plant_batch); the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown in the gait rule;
+ * terrain-normal footholds.  (Stiction: the calls of the next section.) */
 typedef struct wbc_ground_params {
   size_t struct_size;     /* sizeof(wbc_ground_params) of the caller's build */
   double k_n, c_n, c_t;   /* N/m, N s/m, N s/m; all >= 0 and finite */
@@ -592,6 +593,56 @@ int wbc_ground_force_batch(wbc_solver* s, size_t N, const void* q, const void* v
 int wbc_integrate_ground_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
                                const void* normals, const void* height, const void* mu, const void* tau_ext /* may be NULL */, void* f_gr,
                                int* contact /* may be NULL */, void* gap /* may be NULL */, void* stream);
+
+/* Stiction on the ground plant: a per-foot anchor spring.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct, call or default changes;
+ * detect it by these symbols).  The ground plant's friction is viscous, so a loaded foot creeps at F / c_t: it cannot hold a robot on a slope, and
+ * every stance foot of the walking loop drifts.  These two calls are the ground calls with one more term in the tangential force, a spring between the
+ * foot and the world point it is stuck to.  The walking tick becomes
+ *   gait(contact = the previous tick's) -> reference_swing -> step -> integrate_ground_stick     (still four launches, no host work between them).
+ * The new state belongs to the caller and advances IN PLACE:
+ *   anchor [12][N]  solver scalar type; rows 3k .. 3k+2 = the world point foot k is stuck to
+ *   stick  [N]      int.  in: bit k = foot k has an anchor.  out: bit k = foot k is loaded (f_n > 0) and so has an anchor for the next tick; bit 4+k =
+ *                   foot k slid this tick.  Only bits 0-3 are read.  The caller stores 0 before the first tick; anchor needs no initial value.
+ * p_f, v_f, phi, v_n, v_t, f_n, the contact bit and gap are formed exactly as the ground calls form them, from the same words of q, v, Jc, normals,
+ * height, mu and the same wbc_ground_params.  Then, per foot:
+ *   f_n == 0:  f_t = 0;  out bit k = 0, out bit 4+k = 0;  the three anchor words are not touched
+ *   f_n  > 0:  a    = in bit k ? anchor_k : p_f          (first loaded tick: the anchor is dropped where the foot is, e = 0)
+ *              e    = (p_f - a) - n (n . (p_f - a))      (the tangential stretch)
+ *              g    = -k_t e - c_t v_t
+ *              cone = mu_k f_n
+ *              |g| >  cone:  s = cone / |g|;  f_t = s g;  anchor_k := p_f - s e;  out bit 4+k = 1     (slide: the stretch shrinks by the same factor)
+ *              |g| <= cone:  f_t = g;  anchor_k stays (one that was there is not written; a new one = p_f);  out bit 4+k = 0
+ *              out bit k = 1
+ *   f_gr,k = f_n n + f_t
+ * |g| = 0 gives f_t = 0 with no 0/0.  With k_t = 0 the force is the ground calls', as numbers.  The force and the anchor are continuous across the cone
+ * (s = 1 there) and across f_n -> 0 (the cone closes, s -> 0, the anchor follows the foot).
+ * wbc_ground_stick_force_batch evaluates the law alone.  wbc_integrate_ground_stick_batch evaluates it and then advances q, v IN PLACE exactly as
+ * wbc_integrate_batch with f = f_gr does, in ONE launch.
+ * The spring is explicit like the rest of the plant.  With a = the largest eigenvalue of dt (Jc M^-1 Jc^T) diag(c_t, c_t, c_n) over the twelve foot rows
+ * (0.97 with the defaults) and b = that of dt^2 (Jc M^-1 Jc^T) diag(k_t, k_t, k_n), one mode of the semi-implicit step is stable while b < 4 - 2 a.
+ * The default
+ *   k_t = 2e4 N/m   (= k_n)
+ * was fixed on the CPU with the numpy restatement of this law (tests/stick_ref.py) at dt = 1e-3 and 2^-10: a standing robot on planes tilted by
+ * 0.2 rad, which slides 6 cm/s for ever under the viscous law, stops; the walking loop's stance feet slip less than half as far.
+ * tests/test_stick_oracle.py holds the measured figures, a and b among them.  A caller with another dt or a lighter leg scales k_t with m_eff / dt^2.
+ * Stream rules as for the ground calls: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at the buffers; a
+ * NULL required pointer (anchor and stick included): WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
+ * Out of scope: the payload plant (wbc_integrate_plant_batch); the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown in the gait rule;
+ * terrain-normal footholds. */
+typedef struct wbc_stiction_params {
+  size_t struct_size;     /* sizeof(wbc_stiction_params) of the caller's build */
+  double k_t;             /* N/m, >= 0 and finite */
+} wbc_stiction_params;
+void wbc_stiction_params_default(wbc_stiction_params* p);
+/* a negative or non-finite value: WBC_E_INVALID.  The value travels as a kernel argument: nothing is uploaded, later stiction calls use it.  Not inside a
+ * stream capture (a captured graph keeps the value it was captured with). */
+int wbc_solver_set_stiction_params(wbc_solver* s, const wbc_stiction_params* p);
+int wbc_ground_stick_force_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height,
+                                 const void* mu, void* anchor, int* stick, void* f_gr, int* contact /* may be NULL */, void* gap /* may be NULL */,
+                                 void* stream);
+int wbc_integrate_ground_stick_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
+                                     const void* normals, const void* height, const void* mu, const void* tau_ext /* may be NULL */, void* anchor,
+                                     int* stick, void* f_gr, int* contact /* may be NULL */, void* gap /* may be NULL */, void* stream);
 
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and

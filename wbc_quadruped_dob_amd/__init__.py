@@ -271,6 +271,13 @@ def lib():
             L.wbc_solver_set_ground_params.argtypes = [C.c_void_p, C.c_void_p]
             L.wbc_ground_force_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 10
             L.wbc_integrate_ground_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 14
+        # stiction on the ground plant: additive to ABI 10, detected by the symbols in the same way (_stick_lib)
+        if hasattr(L, "wbc_integrate_ground_stick_batch"):
+            L.wbc_stiction_params_default.argtypes = [C.c_void_p]
+            L.wbc_stiction_params_default.restype = None
+            L.wbc_solver_set_stiction_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_ground_stick_force_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 12
+            L.wbc_integrate_ground_stick_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 16
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -321,6 +328,14 @@ def _ground_lib():
     L = lib()
     if not hasattr(L, "wbc_integrate_ground_batch"):
         raise RuntimeError("%s lacks the ground-plant entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+def _stick_lib():
+    """lib(), for the stiction calls of the ground plant: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_integrate_ground_stick_batch"):
+        raise RuntimeError("%s lacks the stiction entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     return L
 
 
@@ -423,6 +438,30 @@ class GroundParams(C.Structure):
 
     def as_dict(self):
         return dict(k_n=self.k_n, c_n=self.c_n, c_t=self.c_t, f_touch=self.f_touch)
+
+
+class StictionParams(C.Structure):
+    """wbc_stiction_params: the anchor spring of the ground plant's stiction calls (include/wbc_hip.h, "Stiction on the ground plant")"""
+    _fields_ = [("struct_size", C.c_size_t), ("k_t", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = StictionParams()
+        _stick_lib().wbc_stiction_params_default(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d):
+        """key k_t; a missing key keeps the default"""
+        p = StictionParams.default()
+        for k, val in d.items():
+            if k != "k_t":
+                raise KeyError("StictionParams has no field %r" % k)
+            setattr(p, k, float(val))
+        return p
+
+    def as_dict(self):
+        return dict(k_t=self.k_t)
 
 
 GAIT_CMD_WORDS = 4   # include/wbc_hip.h: WBC_GAIT_CMD_WORDS -- cmd [GAIT_CMD_WORDS, N]: vx, vy (heading frame), wz, z_g
@@ -1017,6 +1056,47 @@ class Solver:
                                                         self._ptr(tau_ext, m.nv, N), self._ptr(f_gr, 3 * m.nf, N),
                                                         self._ptr(contact, 1, N, self.torch.int32), self._ptr(gap, m.nf, N), self._stream()),
                "wbc_integrate_ground_batch")
+        return dict(f_gr=f_gr, contact=contact, gap=gap)
+
+    def set_stiction_params(self, p):
+        """p: StictionParams or dict (see StictionParams.from_dict): the anchor spring of every later stiction call of this solver."""
+        if isinstance(p, dict):
+            p = StictionParams.from_dict(p)
+        _check(_stick_lib().wbc_solver_set_stiction_params(self._h, C.byref(p)), "wbc_solver_set_stiction_params")
+
+    def ground_stick_force(self, q, v, Jc, normals, height, mu, anchor, stick, f_gr=None, contact=None, gap=None, want_contact=True, want_gap=False):
+        """ground_force() with the per-foot anchor spring (wbc_ground_stick_force_batch).  anchor [12, N] and stick [N] int32 are the caller's and
+        advance IN PLACE: stick in = bit k set where foot k has an anchor (store 0 before the first tick), out = bit k loaded, bit 4+k slid this tick.
+        Returns dict(f_gr, contact, gap)."""
+        m = self.model
+        N = q.shape[1]
+        if anchor is None or stick is None:
+            raise ValueError("anchor and stick are required in/out tensors")
+        f_gr, contact, gap = self._ground_out(N, f_gr, contact, gap, want_contact, want_gap, q.device)
+        _check(_stick_lib().wbc_ground_stick_force_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(Jc, 3 * m.nf * m.nv, N),
+                                                         self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N),
+                                                         self._ptr(anchor, 3 * m.nf, N), self._ptr(stick, 1, N, self.torch.int32),
+                                                         self._ptr(f_gr, 3 * m.nf, N), self._ptr(contact, 1, N, self.torch.int32),
+                                                         self._ptr(gap, m.nf, N), self._stream()), "wbc_ground_stick_force_batch")
+        return dict(f_gr=f_gr, contact=contact, gap=gap)
+
+    def integrate_ground_stick(self, q, v, M, h, Jc, tau, normals, height, mu, anchor, stick, tau_ext=None, f_gr=None, contact=None, gap=None,
+                               want_contact=True, want_gap=False):
+        """ground_stick_force() followed by integrate(f = f_gr), as one launch (wbc_integrate_ground_stick_batch): q, v, anchor and stick advance
+        IN PLACE.  Returns dict(f_gr, contact, gap); pass contact to the next tick's gait()."""
+        m = self.model
+        N = q.shape[1]
+        if anchor is None or stick is None:
+            raise ValueError("anchor and stick are required in/out tensors")
+        f_gr, contact, gap = self._ground_out(N, f_gr, contact, gap, want_contact, want_gap, q.device)
+        _check(_stick_lib().wbc_integrate_ground_stick_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
+                                                             self._ptr(M, m.nv * (m.nv + 1) // 2, N), self._ptr(h, m.nv, N),
+                                                             self._ptr(Jc, 3 * m.nf * m.nv, N), self._ptr(tau, m.nj, N),
+                                                             self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N),
+                                                             self._ptr(tau_ext, m.nv, N), self._ptr(anchor, 3 * m.nf, N),
+                                                             self._ptr(stick, 1, N, self.torch.int32), self._ptr(f_gr, 3 * m.nf, N),
+                                                             self._ptr(contact, 1, N, self.torch.int32), self._ptr(gap, m.nf, N), self._stream()),
+               "wbc_integrate_ground_stick_batch")
         return dict(f_gr=f_gr, contact=contact, gap=gap)
 
     def rollout_tracking(self, horizon, q, v, plan, normals, mu, mask, out, w_des, vdot_des, obs_integ=None, obs_r=None,

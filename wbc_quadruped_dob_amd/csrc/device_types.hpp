@@ -241,6 +241,21 @@ template <class T> struct GroundArgs {   // ground_force_kernel
   GroundIO<T> g;
 };
 template <class T> struct GroundIntegrateArgs : IntegrateArgs<T> { GroundIO<T> g; };   // ground_integrate_kernel (IntegrateArgs::f is not read)
+// stiction on the ground plant (stick.hip.hpp): the per-foot anchor state, advanced in place, and the spring's stiffness -- BY VALUE like GroundIO
+// (wbc_solver_set_stiction_params only fills the solver's host copy)
+template <class T> struct StickIO {
+  T* anchor;    // [12][N] in/out: rows 3k .. 3k+2 = the world point foot k is stuck to
+  int* stick;   // [N] in/out: in bit k = foot k has an anchor; out bit k = loaded, bit 4+k = slid
+  T k_t;
+};
+template <class T> struct StickArgs {   // stick_force_kernel
+  size_t N;
+  const T* q; const T* v; const T* Jc;
+  unsigned long long jpack;   // see SweepArgs::jpack
+  GroundIO<T> g;
+  StickIO<T> s;
+};
+template <class T> struct StickIntegrateArgs : IntegrateArgs<T> { GroundIO<T> g; StickIO<T> s; };   // stick_integrate_kernel (IntegrateArgs::f is not read)
 
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc

@@ -8,15 +8,15 @@
 //   g   = -c_t v_t;   f_t = g scaled back onto the cone |f_t| <= mu f_n (mu UNSCALED: mu_scale belongs to the QP's pyramid);  |g| = 0 -> f_t = 0
 //   f_gr = f_n n + f_t,   contact bit = f_n > f_touch
 // The force acts on EVERY foot whatever the controller's mask says; the commanded f is no input.  Viscous friction has no stiction: a foot under a
-// tangential load F creeps at F / c_t.
+// tangential load F creeps at F / c_t (the anchor spring that holds it: stick.hip.hpp, wbc_ground_stick_force_batch).
 // Same lane mapping as the gait and integrate kernels (lane = 16*leg + state, one wavefront per workgroup): a lane evaluates its foot and stores its three
 // rows of f_gr and its gap; the four lanes of a state combine their bits with one wave64 ballot (gait_gather) and the leg-0 lane stores contact.  Lanes
 // beyond the batch recompute its last state and store nothing.
 // ground_integrate_kernel: the law, then integrate_body<.., GROUND> with the lane's force in registers -- f_gr is stored for the caller, never read back.
 // q, v advance in place: every lane has loaded what the law reads before any lane of its wavefront stores the new state, and a state's four lanes share
 // a wavefront.
-// Out of scope: the payload plant, the rollout kernels and wbc_rollout_*, wbc_multi_*, stiction (a stateful anchor spring), late touchdown in the gait
-// rule, terrain-normal footholds.
+// Out of scope: the payload plant, the rollout kernels and wbc_rollout_*, wbc_multi_*, late touchdown in the gait rule, terrain-normal footholds.
+// (Stiction is stick.hip.hpp's.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_types.hpp"

@@ -138,5 +138,9 @@ template <class T> hipError_t k_gait(const LaunchCtx& L, const DevModel<T>* mode
 // ground_integrate_kernel<T> is the same law followed by k_integrate with f = f_gr handed over in registers -- one launch
 template <class T> hipError_t k_ground_force(const LaunchCtx& L, const DevModel<T>* model, const GroundArgs<T>& a);
 template <class T> hipError_t k_ground_integrate(const LaunchCtx& L, const DevModel<T>* model, const GroundIntegrateArgs<T>& a);
+// stiction on the ground plant (stick.hip.hpp): stick_force_kernel<T> is the contact law with the per-foot anchor spring (anchor, stick advance in
+// place); stick_integrate_kernel<T> is that law followed by k_integrate with f = f_gr handed over in registers -- one launch
+template <class T> hipError_t k_stick_force(const LaunchCtx& L, const DevModel<T>* model, const StickArgs<T>& a);
+template <class T> hipError_t k_stick_integrate(const LaunchCtx& L, const DevModel<T>* model, const StickIntegrateArgs<T>& a);
 
 }  // namespace wbc

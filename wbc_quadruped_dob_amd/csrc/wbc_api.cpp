@@ -95,6 +95,7 @@ struct wbc_solver {
   wbc_swing_params swing;    // the gains of the swing-foot references (wbc_solver_set_swing_params; kernel arguments by value), defaults at creation
   void* d_swing_one = nullptr;   // wbc_compute_swing_reference's staging: SWING_ONE_SCALARS scalars + the mask
   wbc_ground_params ground;  // the contact law of the ground plant (wbc_solver_set_ground_params; kernel arguments by value), the defaults at creation
+  wbc_stiction_params stiction;  // the anchor spring of the ground plant's stiction calls (wbc_solver_set_stiction_params; a kernel argument by value)
   wbc_gait_params gait;      // the schedule of the gait scheduler (wbc_solver_set_gait_params; kernel arguments by value), the model's defaults at creation
   void* d_gait_one = nullptr;    // wbc_compute_gait's staging: GAIT_ONE_SCALARS scalars + contact, mask, events
   // torque-limit post-pass (wbc_limit_torques_batch): the limits travel as a kernel argument like the score weights
@@ -675,6 +676,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   wbc_swing_params_default(&s->swing);
   wbc_gait_params_default(m, &s->gait);
   wbc_ground_params_default(&s->ground);
+  wbc_stiction_params_default(&s->stiction);
   for (int j = 0; j < WBC_MAXV; ++j) s->model_effort[j] = (j < m->fm.nj() && j < (int)m->fm.effort_limit.size()) ? m->fm.effort_limit[j] : HUGE_VAL;
   std::memcpy(s->tau_max, s->model_effort, sizeof(s->tau_max));
   s->limit_grid = limit_qp_grid(prop.multiProcessorCount);
@@ -1667,6 +1669,82 @@ extern "C" int wbc_integrate_ground_batch(wbc_solver* s, size_t N, void* q, void
   hipStream_t st = (hipStream_t)stream;
   return s->dtype == WBC_F64 ? integrate_ground_impl<double>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, f_gr, contact, gap, st)
                              : integrate_ground_impl<float>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, f_gr, contact, gap, st);
+}
+
+// ---- stiction on the ground plant: the anchor spring's stiffness, the law alone, the law + forward dynamics as one launch
+extern "C" void wbc_stiction_params_default(wbc_stiction_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->k_t = 2e4;   // how it was fixed: include/wbc_hip.h
+}
+
+extern "C" int wbc_solver_set_stiction_params(wbc_solver* s, const wbc_stiction_params* p) {
+  if (!s || !p) return fail(WBC_E_INVALID, "null argument");
+  if (p->struct_size < sizeof(wbc_stiction_params)) return fail(WBC_E_INVALID, "wbc_stiction_params: struct_size too small (call wbc_stiction_params_default first)");
+  if (!(p->k_t >= 0) || !std::isfinite(p->k_t)) return fail(WBC_E_INVALID, "wbc_stiction_params: k_t must be finite and >= 0");
+  s->stiction = *p;
+  return WBC_OK;
+}
+
+template <class T>
+static void stick_io(StickIO<T>& k, const wbc_solver* s, void* anchor, int* stick) {
+  k.anchor = (T*)anchor; k.stick = stick; k.k_t = (T)s->stiction.k_t;
+}
+
+template <class T>
+static int ground_stick_force_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height,
+                                   const void* mu, void* anchor, int* stick, void* f_gr, int* contact, void* gap, hipStream_t st) {
+  StickArgs<T> a;
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.Jc = (const T*)Jc; a.jpack = s->jpack;
+  ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
+  stick_io(a.s, s, anchor, stick);
+  LaunchCtx L; L.st = st;
+  hipError_t e = k_stick_force<T>(L, dev_model<T>(s), a);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("ground stick force launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
+extern "C" int wbc_ground_stick_force_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals,
+                                            const void* height, const void* mu, void* anchor, int* stick, void* f_gr, int* contact, void* gap,
+                                            void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !Jc || !normals || !height || !mu || !anchor || !stick || !f_gr) return fail(WBC_E_INVALID, "null argument");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64 ? ground_stick_force_impl<double>(s, N, q, v, Jc, normals, height, mu, anchor, stick, f_gr, contact, gap, st)
+                             : ground_stick_force_impl<float>(s, N, q, v, Jc, normals, height, mu, anchor, stick, f_gr, contact, gap, st);
+}
+
+template <class T>
+static int integrate_ground_stick_impl(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
+                                       const void* normals, const void* height, const void* mu, const void* tau_ext, void* anchor, int* stick,
+                                       void* f_gr, int* contact, void* gap, hipStream_t st) {
+  StickIntegrateArgs<T> a;
+  integrate_args<T>(a, s, N, q, v, M, h, Jc, tau, nullptr, tau_ext, nullptr);   // (zeroes the IntegrateArgs part; f is not read)
+  ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
+  stick_io(a.s, s, anchor, stick);
+  LaunchCtx L; L.st = st;
+  hipError_t e = k_stick_integrate<T>(L, dev_model<T>(s), a);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("integrate ground stick launch: ") + hipGetErrorString(e));
+  return WBC_OK;
+}
+
+extern "C" int wbc_integrate_ground_stick_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
+                                                const void* tau, const void* normals, const void* height, const void* mu, const void* tau_ext,
+                                                void* anchor, int* stick, void* f_gr, int* contact, void* gap, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !M || !h || !Jc || !tau || !normals || !height || !mu || !anchor || !stick || !f_gr) return fail(WBC_E_INVALID, "null argument");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  hipStream_t st = (hipStream_t)stream;
+  return s->dtype == WBC_F64
+             ? integrate_ground_stick_impl<double>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, anchor, stick, f_gr, contact, gap, st)
+             : integrate_ground_stick_impl<float>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, anchor, stick, f_gr, contact, gap, st);
 }
 
 // ---- scored rollouts: the weights, the superset rollout, one tick's cost, the per-group selection
