@@ -1029,6 +1029,14 @@ class Solver:
             gap = self.empty(self.model.nf, N)
         return f_gr, contact, gap
 
+    def _terrain_ptrs(self, N, normals, height, mu):
+        m = self.model
+        return self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N)
+
+    def _ground_out_ptrs(self, N, f_gr, contact, gap):
+        m = self.model
+        return self._ptr(f_gr, 3 * m.nf, N), self._ptr(contact, 1, N, self.torch.int32), self._ptr(gap, m.nf, N)
+
     def ground_force(self, q, v, Jc, normals, height, mu, f_gr=None, contact=None, gap=None, want_contact=True, want_gap=False):
         """The contact law alone (wbc_ground_force_batch): the terrain n_k . x = height[k] under every foot pushes back with f_gr [12, N]; contact [N]
         int32 has bit k set where foot k presses harder than f_touch; gap [4, N] is the signed distance (negative = penetration).  Tensors not
@@ -1037,9 +1045,8 @@ class Solver:
         N = q.shape[1]
         f_gr, contact, gap = self._ground_out(N, f_gr, contact, gap, want_contact, want_gap, q.device)
         _check(_ground_lib().wbc_ground_force_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(Jc, 3 * m.nf * m.nv, N),
-                                                    self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N),
-                                                    self._ptr(f_gr, 3 * m.nf, N), self._ptr(contact, 1, N, self.torch.int32),
-                                                    self._ptr(gap, m.nf, N), self._stream()), "wbc_ground_force_batch")
+                                                    *self._terrain_ptrs(N, normals, height, mu), *self._ground_out_ptrs(N, f_gr, contact, gap),
+                                                    self._stream()), "wbc_ground_force_batch")
         return dict(f_gr=f_gr, contact=contact, gap=gap)
 
     def integrate_ground(self, q, v, M, h, Jc, tau, normals, height, mu, tau_ext=None, f_gr=None, contact=None, gap=None, want_contact=True,
@@ -1052,9 +1059,8 @@ class Solver:
         _check(_ground_lib().wbc_integrate_ground_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
                                                         self._ptr(M, m.nv * (m.nv + 1) // 2, N), self._ptr(h, m.nv, N),
                                                         self._ptr(Jc, 3 * m.nf * m.nv, N), self._ptr(tau, m.nj, N),
-                                                        self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N),
-                                                        self._ptr(tau_ext, m.nv, N), self._ptr(f_gr, 3 * m.nf, N),
-                                                        self._ptr(contact, 1, N, self.torch.int32), self._ptr(gap, m.nf, N), self._stream()),
+                                                        *self._terrain_ptrs(N, normals, height, mu), self._ptr(tau_ext, m.nv, N),
+                                                        *self._ground_out_ptrs(N, f_gr, contact, gap), self._stream()),
                "wbc_integrate_ground_batch")
         return dict(f_gr=f_gr, contact=contact, gap=gap)
 
@@ -1074,10 +1080,9 @@ class Solver:
             raise ValueError("anchor and stick are required in/out tensors")
         f_gr, contact, gap = self._ground_out(N, f_gr, contact, gap, want_contact, want_gap, q.device)
         _check(_stick_lib().wbc_ground_stick_force_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(Jc, 3 * m.nf * m.nv, N),
-                                                         self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N),
+                                                         *self._terrain_ptrs(N, normals, height, mu),
                                                          self._ptr(anchor, 3 * m.nf, N), self._ptr(stick, 1, N, self.torch.int32),
-                                                         self._ptr(f_gr, 3 * m.nf, N), self._ptr(contact, 1, N, self.torch.int32),
-                                                         self._ptr(gap, m.nf, N), self._stream()), "wbc_ground_stick_force_batch")
+                                                         *self._ground_out_ptrs(N, f_gr, contact, gap), self._stream()), "wbc_ground_stick_force_batch")
         return dict(f_gr=f_gr, contact=contact, gap=gap)
 
     def integrate_ground_stick(self, q, v, M, h, Jc, tau, normals, height, mu, anchor, stick, tau_ext=None, f_gr=None, contact=None, gap=None,
@@ -1092,10 +1097,9 @@ class Solver:
         _check(_stick_lib().wbc_integrate_ground_stick_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
                                                              self._ptr(M, m.nv * (m.nv + 1) // 2, N), self._ptr(h, m.nv, N),
                                                              self._ptr(Jc, 3 * m.nf * m.nv, N), self._ptr(tau, m.nj, N),
-                                                             self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(mu, m.nf, N),
-                                                             self._ptr(tau_ext, m.nv, N), self._ptr(anchor, 3 * m.nf, N),
-                                                             self._ptr(stick, 1, N, self.torch.int32), self._ptr(f_gr, 3 * m.nf, N),
-                                                             self._ptr(contact, 1, N, self.torch.int32), self._ptr(gap, m.nf, N), self._stream()),
+                                                             *self._terrain_ptrs(N, normals, height, mu), self._ptr(tau_ext, m.nv, N),
+                                                             self._ptr(anchor, 3 * m.nf, N), self._ptr(stick, 1, N, self.torch.int32),
+                                                             *self._ground_out_ptrs(N, f_gr, contact, gap), self._stream()),
                "wbc_integrate_ground_stick_batch")
         return dict(f_gr=f_gr, contact=contact, gap=gap)
 

@@ -29,31 +29,35 @@ namespace wbc {
 WBC_DEV double ground_sqrt(double x) { return sqrt(x); }
 WBC_DEV float ground_sqrt(float x) { return sqrtf(x); }
 
+// where a lane's words lie in the [rows][N] arrays: row `comp` of its state, and row c0 + stride * leg of it (its foot's block of `stride` rows).
+// (An index, not the word: the load stays on the caller's __restrict__ pointer.)
+struct FootAddr {
+  size_t N; unsigned legN, s32;
+  WBC_DEV FootAddr(int leg, unsigned s32_, unsigned N32) : N(N32), legN((unsigned)leg * N32), s32(s32_) {}
+  WBC_DEV size_t row(int comp) const { return (size_t)comp * N + s32; }
+  WBC_DEV size_t leg_row(int c0, int stride) const { return (size_t)c0 * N + (size_t)((unsigned)stride * legN + s32); }
+};
+
 // one lane's foot: returns f_gr, leaves the gap in `phi` and the bit in `touch`.  s32 = the state the lane computes, N32 = the batch size.
 template <class T>
 WBC_DEV V3<T> ground_law(const T* __restrict__ q, const T* __restrict__ v, const T* __restrict__ Jc, const GroundIO<T>& g, unsigned long long jpack,
                          int leg, unsigned s32, unsigned N32, T& phi, bool& touch) {
-  const size_t N = N32;
-  const unsigned legN = (unsigned)leg * N32;
-#define GLD(ptr, comp) ((ptr)[(size_t)(comp) * N + s32])
-#define GLL(ptr, c0, stride) ((ptr)[(size_t)(c0) * N + (size_t)((unsigned)(stride) * legN + s32)])
+  const FootAddr A(leg, s32, N32);
   int jx[3];
   jidx_of_leg((const DevModel<T>*)nullptr, jpack, leg, jx);
   // the words integrate_body phase 1 loads: the lever arm from the base-angular block -[d]x of my foot's rows, the own-leg Jacobian block
-  const V3<T> dl = mk<T>(GLL(Jc, 18 * 1 + 5, 54), GLL(Jc, 18 * 2 + 3, 54), GLL(Jc, 18 * 0 + 4, 54));
+  const V3<T> dl = mk<T>(Jc[A.leg_row(18 * 1 + 5, 54)], Jc[A.leg_row(18 * 2 + 3, 54)], Jc[A.leg_row(18 * 0 + 4, 54)]);
   T jcl[3][3], qd[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int col = 6 + jx[k];
-    jcl[0][k] = GLL(Jc, 0 + col, 54); jcl[1][k] = GLL(Jc, 18 + col, 54); jcl[2][k] = GLL(Jc, 36 + col, 54);
-    qd[k] = GLD(v, col);
+    jcl[0][k] = Jc[A.leg_row(0 + col, 54)]; jcl[1][k] = Jc[A.leg_row(18 + col, 54)]; jcl[2][k] = Jc[A.leg_row(36 + col, 54)];
+    qd[k] = v[A.row(col)];
   }
-  const V3<T> pb = mk<T>(GLD(q, 0), GLD(q, 1), GLD(q, 2));
-  const V3<T> vb = mk<T>(GLD(v, 0), GLD(v, 1), GLD(v, 2)), om = mk<T>(GLD(v, 3), GLD(v, 4), GLD(v, 5));
-  const V3<T> n = mk<T>(GLL(g.normals, 0, 3), GLL(g.normals, 1, 3), GLL(g.normals, 2, 3));
-  const T d = GLL(g.height, 0, 1), mu = GLL(g.mu, 0, 1);
-#undef GLL
-#undef GLD
+  const V3<T> pb = mk<T>(q[A.row(0)], q[A.row(1)], q[A.row(2)]);
+  const V3<T> vb = mk<T>(v[A.row(0)], v[A.row(1)], v[A.row(2)]), om = mk<T>(v[A.row(3)], v[A.row(4)], v[A.row(5)]);
+  const V3<T> n = mk<T>(g.normals[A.leg_row(0, 3)], g.normals[A.leg_row(1, 3)], g.normals[A.leg_row(2, 3)]);
+  const T d = g.height[A.leg_row(0, 1)], mu = g.mu[A.leg_row(0, 1)];
   const V3<T> pf = pb + dl;
   const V3<T> vf = vb + cross(om, dl) + mk<T>(jcl[0][0] * qd[0] + jcl[0][1] * qd[1] + jcl[0][2] * qd[2],
                                               jcl[1][0] * qd[0] + jcl[1][1] * qd[1] + jcl[1][2] * qd[2],
@@ -84,32 +88,35 @@ WBC_DEV void ground_store(const GroundIO<T>& g, int leg, unsigned st, unsigned s
   }
 }
 
-template <class T>
-__global__ __launch_bounds__(64) void ground_force_kernel(GroundArgs<T> a) {
+// the four kernels' lane mapping: lane = 16 * leg + state, one wavefront per workgroup.  Lanes beyond the batch recompute its last state (the state
+// integrate_body gives the same lane) and store nothing.
+struct FootLane { int leg; unsigned st, s32; bool live; };
+WBC_DEV FootLane foot_lane(size_t N) {
   unsigned tx = threadIdx.x;
   asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
-  const int leg = (int)((tx & 63) >> 4);
-  const unsigned st = tx & 15;
-  const size_t s_raw = (size_t)blockIdx.x * 16 + st;
-  const bool live = s_raw < a.N;
-  const unsigned s32 = (unsigned)(live ? s_raw : a.N - 1);   // lanes beyond the batch recompute its last state and store nothing
+  FootLane l;
+  l.leg = (int)((tx & 63) >> 4);
+  l.st = tx & 15;
+  const size_t s_raw = (size_t)blockIdx.x * 16 + l.st;
+  l.live = s_raw < N;
+  l.s32 = (unsigned)(l.live ? s_raw : N - 1);
+  return l;
+}
+
+template <class T>
+__global__ __launch_bounds__(64) void ground_force_kernel(GroundArgs<T> a) {
+  const FootLane l = foot_lane(a.N);
   T phi; bool touch;
-  const V3<T> f = ground_law<T>(a.q, a.v, a.Jc, a.g, a.jpack, leg, s32, (unsigned)a.N, phi, touch);
-  ground_store<T>(a.g, leg, st, s32, (unsigned)a.N, live, f, phi, touch);
+  const V3<T> f = ground_law<T>(a.q, a.v, a.Jc, a.g, a.jpack, l.leg, l.s32, (unsigned)a.N, phi, touch);
+  ground_store<T>(a.g, l.leg, l.st, l.s32, (unsigned)a.N, l.live, f, phi, touch);
 }
 
 template <class T>
 __global__ __launch_bounds__(64) void ground_integrate_kernel(const DevModel<T>* __restrict__ model, GroundIntegrateArgs<T> a) {
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));
-  const int leg = (int)((tx & 63) >> 4);
-  const unsigned st = tx & 15;
-  const size_t s_raw = (size_t)blockIdx.x * 16 + st;
-  const bool live = s_raw < a.N;
-  const unsigned s32 = (unsigned)(live ? s_raw : a.N - 1);   // (the state integrate_body gives the same lane)
+  const FootLane l = foot_lane(a.N);
   T phi; bool touch;
-  const V3<T> f = ground_law<T>(a.q, a.v, a.Jc, a.g, a.jpack, leg, s32, (unsigned)a.N, phi, touch);
-  ground_store<T>(a.g, leg, st, s32, (unsigned)a.N, live, f, phi, touch);
+  const V3<T> f = ground_law<T>(a.q, a.v, a.Jc, a.g, a.jpack, l.leg, l.s32, (unsigned)a.N, phi, touch);
+  ground_store<T>(a.g, l.leg, l.st, l.s32, (unsigned)a.N, l.live, f, phi, touch);
   integrate_body<T, 16, IntegrateNoWait, 0, false, false, false, IntegrateNoWait, false, false, false, true>(
       model, a, IntegrateNoWait(), nullptr, nullptr, nullptr, IntegrateNoWait(), nullptr, nullptr, f);
 }

@@ -1,8 +1,10 @@
 // Stiction on the ground plant (include/wbc_hip.h at wbc_ground_stick_force_batch): the contact law of ground.hip.hpp with a per-foot anchor spring,
 // so that a loaded foot holds its place instead of creeping at F / c_t.  The new state is the caller's and advances IN PLACE: anchor [12][N] (rows
 // 3k .. 3k+2 = the world point foot k is stuck to) and stick [N] (in: bit k = foot k has an anchor; out: bit k = loaded, bit 4+k = slid this tick).
-// p_f, v_f, phi, v_n, v_t, f_n, the contact bit and the gap are formed exactly as ground_law forms them (the lines are restated here and not shared,
-// so that k_ground's device code stays what it was).  Then, per foot:
+// p_f, v_f, phi, v_n, v_t, f_n, the contact bit and the gap are formed exactly as ground_law forms them.  The lines are restated here and not shared:
+// behind a common helper (two shapes tried, docs/DESIGN_HISTORY.md) k_ground assembles as before and this unit keeps its instruction counts, but its
+// loads are scheduled differently and stick_force_kernel measured 5 - 10 % slower.  Only the addresses (FootAddr) and the lane mapping (foot_lane) are
+// ground.hip.hpp's.  Then, per foot:
 //   f_n == 0:  f_t = 0, both out bits clear, the anchor words untouched
 //   f_n  > 0:  a = in bit ? anchor : p_f          (first loaded tick: the anchor is dropped where the foot is)
 //              e = (p_f - a) - n (n . (p_f - a))  g = -k_t e - c_t v_t        cone = mu f_n
@@ -40,29 +42,24 @@ template <class T> struct StickOut {
 template <class T>
 WBC_DEV V3<T> stick_law(const T* __restrict__ q, const T* __restrict__ v, const T* __restrict__ Jc, const GroundIO<T>& g, const StickIO<T>& sk,
                         unsigned long long jpack, int leg, unsigned s32, unsigned N32, StickOut<T>& o) {
-  const size_t N = N32;
-  const unsigned legN = (unsigned)leg * N32;
-#define GLD(ptr, comp) ((ptr)[(size_t)(comp) * N + s32])
-#define GLL(ptr, c0, stride) ((ptr)[(size_t)(c0) * N + (size_t)((unsigned)(stride) * legN + s32)])
+  const FootAddr A(leg, s32, N32);
   int jx[3];
   jidx_of_leg((const DevModel<T>*)nullptr, jpack, leg, jx);
-  // (ground_law's loads and arithmetic, word for word, down to f_n)
-  const V3<T> dl = mk<T>(GLL(Jc, 18 * 1 + 5, 54), GLL(Jc, 18 * 2 + 3, 54), GLL(Jc, 18 * 0 + 4, 54));
+  // (ground_law's loads and arithmetic, word for word, down to f_n: a change there is a change here, contraction included)
+  const V3<T> dl = mk<T>(Jc[A.leg_row(18 * 1 + 5, 54)], Jc[A.leg_row(18 * 2 + 3, 54)], Jc[A.leg_row(18 * 0 + 4, 54)]);
   T jcl[3][3], qd[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int col = 6 + jx[k];
-    jcl[0][k] = GLL(Jc, 0 + col, 54); jcl[1][k] = GLL(Jc, 18 + col, 54); jcl[2][k] = GLL(Jc, 36 + col, 54);
-    qd[k] = GLD(v, col);
+    jcl[0][k] = Jc[A.leg_row(0 + col, 54)]; jcl[1][k] = Jc[A.leg_row(18 + col, 54)]; jcl[2][k] = Jc[A.leg_row(36 + col, 54)];
+    qd[k] = v[A.row(col)];
   }
-  const V3<T> pb = mk<T>(GLD(q, 0), GLD(q, 1), GLD(q, 2));
-  const V3<T> vb = mk<T>(GLD(v, 0), GLD(v, 1), GLD(v, 2)), om = mk<T>(GLD(v, 3), GLD(v, 4), GLD(v, 5));
-  const V3<T> n = mk<T>(GLL(g.normals, 0, 3), GLL(g.normals, 1, 3), GLL(g.normals, 2, 3));
-  const T d = GLL(g.height, 0, 1), mu = GLL(g.mu, 0, 1);
-  const V3<T> a_in = mk<T>(GLL(sk.anchor, 0, 3), GLL(sk.anchor, 1, 3), GLL(sk.anchor, 2, 3));
+  const V3<T> pb = mk<T>(q[A.row(0)], q[A.row(1)], q[A.row(2)]);
+  const V3<T> vb = mk<T>(v[A.row(0)], v[A.row(1)], v[A.row(2)]), om = mk<T>(v[A.row(3)], v[A.row(4)], v[A.row(5)]);
+  const V3<T> n = mk<T>(g.normals[A.leg_row(0, 3)], g.normals[A.leg_row(1, 3)], g.normals[A.leg_row(2, 3)]);
+  const T d = g.height[A.leg_row(0, 1)], mu = g.mu[A.leg_row(0, 1)];
+  const V3<T> a_in = mk<T>(sk.anchor[A.leg_row(0, 3)], sk.anchor[A.leg_row(1, 3)], sk.anchor[A.leg_row(2, 3)]);
   const bool had = ((sk.stick[s32] >> leg) & 1) != 0;
-#undef GLL
-#undef GLD
   const V3<T> pf = pb + dl;
   const V3<T> vf = vb + cross(om, dl) + mk<T>(jcl[0][0] * qd[0] + jcl[0][1] * qd[1] + jcl[0][2] * qd[2],
                                               jcl[1][0] * qd[0] + jcl[1][1] * qd[1] + jcl[1][2] * qd[2],
@@ -119,30 +116,18 @@ WBC_DEV void stick_store(const GroundIO<T>& g, const StickIO<T>& sk, int leg, un
 
 template <class T>
 __global__ __launch_bounds__(64) void stick_force_kernel(StickArgs<T> a) {
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
-  const int leg = (int)((tx & 63) >> 4);
-  const unsigned st = tx & 15;
-  const size_t s_raw = (size_t)blockIdx.x * 16 + st;
-  const bool live = s_raw < a.N;
-  const unsigned s32 = (unsigned)(live ? s_raw : a.N - 1);   // lanes beyond the batch recompute its last state and store nothing
+  const FootLane l = foot_lane(a.N);
   StickOut<T> o;
-  const V3<T> f = stick_law<T>(a.q, a.v, a.Jc, a.g, a.s, a.jpack, leg, s32, (unsigned)a.N, o);
-  stick_store<T>(a.g, a.s, leg, st, s32, (unsigned)a.N, live, f, o);
+  const V3<T> f = stick_law<T>(a.q, a.v, a.Jc, a.g, a.s, a.jpack, l.leg, l.s32, (unsigned)a.N, o);
+  stick_store<T>(a.g, a.s, l.leg, l.st, l.s32, (unsigned)a.N, l.live, f, o);
 }
 
 template <class T>
 __global__ __launch_bounds__(64) void stick_integrate_kernel(const DevModel<T>* __restrict__ model, StickIntegrateArgs<T> a) {
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));
-  const int leg = (int)((tx & 63) >> 4);
-  const unsigned st = tx & 15;
-  const size_t s_raw = (size_t)blockIdx.x * 16 + st;
-  const bool live = s_raw < a.N;
-  const unsigned s32 = (unsigned)(live ? s_raw : a.N - 1);   // (the state integrate_body gives the same lane)
+  const FootLane l = foot_lane(a.N);
   StickOut<T> o;
-  const V3<T> f = stick_law<T>(a.q, a.v, a.Jc, a.g, a.s, a.jpack, leg, s32, (unsigned)a.N, o);
-  stick_store<T>(a.g, a.s, leg, st, s32, (unsigned)a.N, live, f, o);
+  const V3<T> f = stick_law<T>(a.q, a.v, a.Jc, a.g, a.s, a.jpack, l.leg, l.s32, (unsigned)a.N, o);
+  stick_store<T>(a.g, a.s, l.leg, l.st, l.s32, (unsigned)a.N, l.live, f, o);
   integrate_body<T, 16, IntegrateNoWait, 0, false, false, false, IntegrateNoWait, false, false, false, true>(
       model, a, IntegrateNoWait(), nullptr, nullptr, nullptr, IntegrateNoWait(), nullptr, nullptr, f);
 }

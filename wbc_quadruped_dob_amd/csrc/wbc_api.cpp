@@ -450,22 +450,15 @@ static TickPlan plan_tick(int dtype, int observer_order, const wbc_solver_option
     p.fused = 3;
     return p;
   }
-  if (tt32n && !warm && N >= r.tt_first_min) {
-    p.fused = 2; p.front = 0; p.pack2 = 1; p.sweep_block = 64; p.qp = 1; p.tile = wbc::tile_tick_states(N); p.qp_body = 2;
-    return p;
+  // the tile tick's plan, stated once (at most one of the four holds: they differ in scalar type and observer).  Observer on: the sweep | observer roles in
+  // front; fp32: the packed sweep; the states per workgroup are the kernel's own.  It goes in front of the one-launch tick from tt_first_min on, behind it otherwise.
+  TickPlan tt{};
+  const bool tile_tick = tt32n || tt32 || tt64 || tt64o;
+  if (tile_tick) {
+    tt.fused = 2; tt.front = ob ? 4 : 0; tt.obs_split = ob; tt.pack2 = f32; tt.sweep_block = 64; tt.qp = 1; tt.qp_body = 2;
+    tt.tile = f32 ? wbc::tile_tick_states(N) : (ob ? wbc::tile_tick_states_f64_obs(N) : wbc::tile_tick_states_f64(N));
   }
-  if (tt32 && !warm && N >= r.tt_first_min) {
-    p.fused = 2; p.front = 4; p.obs_split = true; p.pack2 = 1; p.sweep_block = 64; p.qp = 1; p.tile = wbc::tile_tick_states(N); p.qp_body = 2;
-    return p;
-  }
-  if (tt64 && !warm && N >= r.tt_first_min) {
-    p.fused = 2; p.front = 0; p.sweep_block = 64; p.qp = 1; p.tile = wbc::tile_tick_states_f64(N); p.qp_body = 2;
-    return p;
-  }
-  if (tt64o && !warm && N >= r.tt_first_min) {
-    p.fused = 2; p.front = 4; p.obs_split = true; p.sweep_block = 64; p.qp = 1; p.tile = wbc::tile_tick_states_f64_obs(N); p.qp_body = 2;
-    return p;
-  }
+  if (tile_tick && !warm && N >= r.tt_first_min) return tt;
   if ((mats || !pf) && N <= (ob ? r.fused_max_obs : r.fused_max_noobs)) {
     // small batch: one launch, 16 states per workgroup, rnea_step | mass_jac | [observer] | QP as wavefront roles and the
     // workspace through LDS (fused_tick.hip.hpp)
@@ -473,25 +466,10 @@ static TickPlan plan_tick(int dtype, int observer_order, const wbc_solver_option
     p.qp_warm = warm;
     return p;
   }
-  if (tt64) {
-    p.fused = 2; p.front = 0; p.sweep_block = 64; p.qp = 1; p.tile = wbc::tile_tick_states_f64(N); p.qp_body = 2;
-    return p;
-  }
-  if (tt64o) {
-    p.fused = 2; p.front = 4; p.obs_split = true; p.sweep_block = 64; p.qp = 1; p.tile = wbc::tile_tick_states_f64_obs(N); p.qp_body = 2;
-    return p;
-  }
-  if (tt32n) {
-    p.fused = 2; p.front = 0; p.pack2 = 1; p.sweep_block = 64; p.qp = 1; p.tile = wbc::tile_tick_states(N); p.qp_body = 2;
-    return p;
-  }
-  if (tt32) {
-    // mid-size fp32 observer-on batch: sweep | observer roles and the staged QP tile of the same 128 states per workgroup, one launch (tile_tick.hip.hpp).
-    // (warm ticks: only where the cold tiles are the plan anyway -- the kernel reports the sets; from warm_lane_min on the warm per-lane pair stays faster:
-    //  230 against 250 us at 262 144 states)
-    p.fused = 2; p.front = 4; p.obs_split = true; p.pack2 = 1; p.sweep_block = 64; p.qp = 1; p.tile = wbc::tile_tick_states(N); p.qp_body = 2;
-    return p;
-  }
+  // tt32: mid-size fp32 observer-on batch: sweep | observer roles and the staged QP tile of the same 128 states per workgroup, one launch (tile_tick.hip.hpp).
+  // (warm ticks: only where the cold tiles are the plan anyway -- the kernel reports the sets; from warm_lane_min on the warm per-lane pair stays faster:
+  //  230 against 250 us at 262 144 states)
+  if (tile_tick) return tt;
   // Large batches solve the QPs ONE STATE PER LANE first (qp_lane_kernel: semismooth Newton on the residual wrench, 64 QPs
   // per wavefront, no cross-lane traffic); the few per cent it does not finish go through a device-side list to the dense
   // active-set kernel.  No host read: the list length stays on the device, the second launch is grid-stride over it.
@@ -880,6 +858,18 @@ extern "C" int wbc_solver_collect_timing(wbc_solver* s, double* ms, int* launche
 
 template <class T> static const DevModel<T>* dev_model(const wbc_solver* s) { return (const DevModel<T>*)s->d_model; }
 
+// The launch path of the one-launch batch entry points, behind their own argument checks: capacity, the solver's device, the caller's stream, the
+// scalar type, the launch error.  launch(T(), L) fills the kernel's argument struct for the scalar type T and returns the launcher's hipError_t.
+template <class F>
+static int launch_batch(wbc_solver* s, size_t N, void* stream, const char* what, F&& launch) {
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  ON_DEVICE(s);
+  LaunchCtx L; L.st = (hipStream_t)stream;
+  const hipError_t e = s->dtype == WBC_F64 ? launch(double(), L) : launch(float(), L);
+  if (e != hipSuccess) return fail(WBC_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+  return WBC_OK;
+}
+
 // keep_structural: `skip` = this call may leave the structural zeros / ones of M and Jc alone (same buffers and N as the call that
 // last WROTE them).  The buffers are recorded only once the launch that writes them has been enqueued (written()); a call that
 // fails before that forgets them, so the next call writes every word again.
@@ -1178,26 +1168,27 @@ extern "C" int wbc_solver_limited_count(wbc_solver* s, int* resolved) {
   return WBC_OK;
 }
 
+// the integrator's launch, with or without a payload on the plant: the public calls' and the per-tick loop's of rollout()
 template <class T>
-static int integrate_impl(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
-                          const void* tau, const void* f, const void* tau_ext, void* tau_traj, hipStream_t st, const void* payload = nullptr) {
+static hipError_t integrate_impl(const LaunchCtx& L, const wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
+                                 const void* tau, const void* f, const void* tau_ext, void* tau_traj, const void* payload) {
   IntegrateArgs<T> a;
   integrate_args(a, s, N, q, v, M, h, Jc, tau, f, tau_ext, tau_traj);
-  LaunchCtx L; L.st = st;
-  hipError_t e = payload ? k_integrate_plant<T>(L, dev_model<T>(s), a, (const T*)payload) : k_integrate<T>(L, dev_model<T>(s), a);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("integrate launch: ") + hipGetErrorString(e));
-  return WBC_OK;
+  return payload ? k_integrate_plant<T>(L, dev_model<T>(s), a, (const T*)payload) : k_integrate<T>(L, dev_model<T>(s), a);
+}
+
+static int integrate_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau, const void* f,
+                           const void* tau_ext, const void* payload, void* stream) {
+  if (!s || !q || !v || !M || !h || !Jc || !tau || !f) return fail(WBC_E_INVALID, "null argument");
+  if (N == 0) return WBC_OK;
+  return launch_batch(s, N, stream, "integrate", [&](auto scalar, const LaunchCtx& L) {
+    return integrate_impl<decltype(scalar)>(L, s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, payload);
+  });
 }
 
 extern "C" int wbc_integrate_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h,
                                    const void* Jc, const void* tau, const void* f, const void* tau_ext, void* stream) {
-  if (!s || !q || !v || !M || !h || !Jc || !tau || !f) return fail(WBC_E_INVALID, "null argument");
-  if (N == 0) return WBC_OK;
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? integrate_impl<double>(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, st)
-                             : integrate_impl<float>(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, st);
+  return integrate_batch(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, stream);
 }
 
 // (ABI 10) the plant's extras of wbc_*_plant_batch: NULL plant = the calls without it; a struct of an older, smaller build is refused
@@ -1214,14 +1205,7 @@ extern "C" int wbc_integrate_plant_batch(wbc_solver* s, size_t N, void* q, void*
   const void *tau_ext, *payload;
   const int rc = plant_args(plant, &tau_ext, &payload);
   if (rc) return rc;
-  if (!payload) return wbc_integrate_batch(s, N, q, v, M, h, Jc, tau, f, tau_ext, stream);
-  if (!s || !q || !v || !M || !h || !Jc || !tau || !f) return fail(WBC_E_INVALID, "null argument");
-  if (N == 0) return WBC_OK;
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? integrate_impl<double>(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, st, payload)
-                             : integrate_impl<float>(s, N, q, v, M, h, Jc, tau, f, tau_ext, nullptr, st, payload);
+  return integrate_batch(s, N, q, v, M, h, Jc, tau, f, tau_ext, payload, stream);
 }
 
 // ---- scored rollouts (score.hip.hpp): the solver's weights and the call's buffers as ONE kernel argument
@@ -1349,9 +1333,10 @@ static int rollout(wbc_solver* s, size_t N, int horizon, const wbc_batch_in* in,
     s->in_rollout = 0;
     if (rc) return rc;
     void* traj = x.tau_traj ? (void*)((char*)x.tau_traj + (size_t)t * nj * N * ts) : nullptr;
-    rc = f64 ? integrate_impl<double>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, x.tau_ext, traj, st, x.payload)
-             : integrate_impl<float>(s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, x.tau_ext, traj, st, x.payload);
-    if (rc) return rc;
+    LaunchCtx L; L.st = st;
+    const hipError_t e = f64 ? integrate_impl<double>(L, s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, x.tau_ext, traj, x.payload)
+                             : integrate_impl<float>(L, s, N, (void*)in->q, (void*)in->v, out->M, out->h, out->Jc, out->tau, out->f, x.tau_ext, traj, x.payload);
+    if (e != hipSuccess) return fail(WBC_E_HIP, std::string("integrate launch: ") + hipGetErrorString(e));
     if (x.score) {
       rc = score_tick(s, N, in->q, in->v, out->tau, out->f, out->status, x.score, t > 0 || x.score->accumulate != 0, t == horizon - 1, st);
       if (rc) return rc;
@@ -1428,27 +1413,17 @@ extern "C" int wbc_solver_set_ref_params(wbc_solver* s, const wbc_ref_params* g)
   return s->dtype == WBC_F64 ? upload_ref<double>(s, g) : upload_ref<float>(s, g);
 }
 
-template <class T>
-static int reference_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, double t, void* w_des,
-                          void* vdot_des, void* com, hipStream_t st) {
-  RefArgs<T> a;
-  ref_args(a, s, N, q, v, plan, t, w_des, vdot_des, com);
-  LaunchCtx L; L.st = st;
-  hipError_t e = k_reference<T>(L, dev_model<T>(s), (const DevRefParams<T>*)s->d_ref, a);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("reference launch: ") + hipGetErrorString(e));
-  return WBC_OK;
-}
-
 extern "C" int wbc_reference_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, double t,
                                    void* w_des, void* vdot_des, void* com, void* stream) {
   if (!s || !q || !v || !plan || !w_des || !vdot_des) return fail(WBC_E_INVALID, "null argument");
   if (!s->d_ref) return fail(WBC_E_INVALID, "call wbc_solver_set_ref_params first");
   if (N == 0) return WBC_OK;
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? reference_impl<double>(s, N, q, v, plan, t, w_des, vdot_des, com, st)
-                             : reference_impl<float>(s, N, q, v, plan, t, w_des, vdot_des, com, st);
+  return launch_batch(s, N, stream, "reference", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    RefArgs<T> a;
+    ref_args(a, s, N, q, v, plan, t, w_des, vdot_des, com);
+    return k_reference<T>(L, dev_model<T>(s), (const DevRefParams<T>*)s->d_ref, a);
+  });
 }
 
 // ---- swing-foot references: the gains, the stand-alone call, the CoM reference generator with the swing law fused in
@@ -1478,42 +1453,19 @@ static void swing_args(SwingArgs<T>& a, const wbc_solver* s, const int* mask, co
   a.P.damping = (T)s->swing.damping;
 }
 
-template <class T>
-static int swing_reference_impl(wbc_solver* s, size_t N, const void* q, const void* v, const int* mask, const void* swing, double t, void* vdot_des,
-                                void* foot, hipStream_t st) {
-  SwingRefArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.t = (T)t; a.vdot_des = (T*)vdot_des; a.jpack = s->jpack;
-  swing_args(a.s, s, mask, swing, foot);
-  LaunchCtx L; L.st = st;
-  hipError_t e = k_swing_reference<T>(L, dev_model<T>(s), a);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("swing reference launch: ") + hipGetErrorString(e));
-  return WBC_OK;
-}
-
 extern "C" int wbc_swing_reference_batch(wbc_solver* s, size_t N, const void* q, const void* v, const int* mask, const void* swing, double t,
                                          void* vdot_des, void* foot, void* stream) {
   if (!s) return fail(WBC_E_INVALID, "null solver");
   if (N == 0) return WBC_OK;
   if (!q || !v || !mask || !swing || !vdot_des) return fail(WBC_E_INVALID, "null argument");
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? swing_reference_impl<double>(s, N, q, v, mask, swing, t, vdot_des, foot, st)
-                             : swing_reference_impl<float>(s, N, q, v, mask, swing, t, vdot_des, foot, st);
-}
-
-template <class T>
-static int reference_swing_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, const int* mask, const void* swing, double t,
-                                void* w_des, void* vdot_des, void* com, void* foot, hipStream_t st) {
-  RefArgs<T> a;
-  ref_args(a, s, N, q, v, plan, t, w_des, vdot_des, com);
-  SwingArgs<T> sa;
-  swing_args(sa, s, mask, swing, foot);
-  LaunchCtx L; L.st = st;
-  hipError_t e = k_reference_swing<T>(L, dev_model<T>(s), (const DevRefParams<T>*)s->d_ref, a, sa);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("reference + swing launch: ") + hipGetErrorString(e));
-  return WBC_OK;
+  return launch_batch(s, N, stream, "swing reference", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    SwingRefArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.t = (T)t; a.vdot_des = (T*)vdot_des; a.jpack = s->jpack;
+    swing_args(a.s, s, mask, swing, foot);
+    return k_swing_reference<T>(L, dev_model<T>(s), a);
+  });
 }
 
 extern "C" int wbc_reference_swing_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* plan, const int* mask, const void* swing,
@@ -1522,11 +1474,14 @@ extern "C" int wbc_reference_swing_batch(wbc_solver* s, size_t N, const void* q,
   if (N == 0) return WBC_OK;
   if (!q || !v || !plan || !mask || !swing || !w_des || !vdot_des) return fail(WBC_E_INVALID, "null argument");
   if (!s->d_ref) return fail(WBC_E_INVALID, "call wbc_solver_set_ref_params first");
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? reference_swing_impl<double>(s, N, q, v, plan, mask, swing, t, w_des, vdot_des, com, foot, st)
-                             : reference_swing_impl<float>(s, N, q, v, plan, mask, swing, t, w_des, vdot_des, com, foot, st);
+  return launch_batch(s, N, stream, "reference + swing", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    RefArgs<T> a;
+    ref_args(a, s, N, q, v, plan, t, w_des, vdot_des, com);
+    SwingArgs<T> sa;
+    swing_args(sa, s, mask, swing, foot);
+    return k_reference_swing<T>(L, dev_model<T>(s), (const DevRefParams<T>*)s->d_ref, a, sa);
+  });
 }
 
 // ---- gait scheduler: the schedule, the batch call (phase, mask and the lifted feet's plan words advance in place)
@@ -1561,38 +1516,28 @@ extern "C" int wbc_solver_set_gait_params(wbc_solver* s, const wbc_gait_params* 
   return WBC_OK;
 }
 
-template <class T>
-static int gait_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact, void* phase, int* mask, void* swing,
-                     int* events, hipStream_t st) {
-  GaitArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.cmd = (const T*)cmd; a.contact = contact;
-  a.phase = (T*)phase; a.mask = mask; a.swing = (T*)swing; a.events = events; a.jpack = s->jpack;
-  const wbc_gait_params& g = s->gait;
-  a.P.dphi = (T)(s->params.dt / g.period); a.P.period = (T)g.period; a.P.clearance = (T)g.clearance; a.P.k_v = (T)g.k_v; a.P.late = (T)g.late;
-  for (int k = 0; k < 4; ++k) {
-    a.P.duty[k] = (T)g.duty[k]; a.P.offset[k] = (T)g.offset[k];
-    a.P.inv_sw[k] = g.duty[k] == 1.0 ? (T)0 : (T)(1.0 / (1.0 - g.duty[k]));
-    a.P.T_sw[k] = (T)((1.0 - g.duty[k]) * g.period);
-    a.P.bx[k] = (T)g.base_xy[k][0]; a.P.by[k] = (T)g.base_xy[k][1];
-  }
-  a.P.retarget = g.retarget;
-  LaunchCtx L; L.st = st;
-  hipError_t e = k_gait<T>(L, dev_model<T>(s), a);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("gait launch: ") + hipGetErrorString(e));
-  return WBC_OK;
-}
-
 extern "C" int wbc_gait_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact, void* phase, int* mask,
                               void* swing, int* events, void* stream) {
   if (!s) return fail(WBC_E_INVALID, "null solver");
   if (N == 0) return WBC_OK;
   if (!q || !v || !cmd || !phase || !mask || !swing) return fail(WBC_E_INVALID, "null argument");
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? gait_impl<double>(s, N, q, v, cmd, contact, phase, mask, swing, events, st)
-                             : gait_impl<float>(s, N, q, v, cmd, contact, phase, mask, swing, events, st);
+  return launch_batch(s, N, stream, "gait", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GaitArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.cmd = (const T*)cmd; a.contact = contact;
+    a.phase = (T*)phase; a.mask = mask; a.swing = (T*)swing; a.events = events; a.jpack = s->jpack;
+    const wbc_gait_params& g = s->gait;
+    a.P.dphi = (T)(s->params.dt / g.period); a.P.period = (T)g.period; a.P.clearance = (T)g.clearance; a.P.k_v = (T)g.k_v; a.P.late = (T)g.late;
+    for (int k = 0; k < 4; ++k) {
+      a.P.duty[k] = (T)g.duty[k]; a.P.offset[k] = (T)g.offset[k];
+      a.P.inv_sw[k] = g.duty[k] == 1.0 ? (T)0 : (T)(1.0 / (1.0 - g.duty[k]));
+      a.P.T_sw[k] = (T)((1.0 - g.duty[k]) * g.period);
+      a.P.bx[k] = (T)g.base_xy[k][0]; a.P.by[k] = (T)g.base_xy[k][1];
+    }
+    a.P.retarget = g.retarget;
+    return k_gait<T>(L, dev_model<T>(s), a);
+  });
 }
 
 // ---- ground-contact plant: the contact law's constants, the law alone, the law + forward dynamics as one launch
@@ -1620,42 +1565,19 @@ static void ground_io(GroundIO<T>& g, const wbc_solver* s, const void* normals, 
   g.P.k_n = (T)s->ground.k_n; g.P.c_n = (T)s->ground.c_n; g.P.c_t = (T)s->ground.c_t; g.P.f_touch = (T)s->ground.f_touch;
 }
 
-template <class T>
-static int ground_force_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height,
-                             const void* mu, void* f_gr, int* contact, void* gap, hipStream_t st) {
-  GroundArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.Jc = (const T*)Jc; a.jpack = s->jpack;
-  ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
-  LaunchCtx L; L.st = st;
-  hipError_t e = k_ground_force<T>(L, dev_model<T>(s), a);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("ground force launch: ") + hipGetErrorString(e));
-  return WBC_OK;
-}
-
 extern "C" int wbc_ground_force_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height,
                                       const void* mu, void* f_gr, int* contact, void* gap, void* stream) {
   if (!s) return fail(WBC_E_INVALID, "null solver");
   if (N == 0) return WBC_OK;
   if (!q || !v || !Jc || !normals || !height || !mu || !f_gr) return fail(WBC_E_INVALID, "null argument");
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? ground_force_impl<double>(s, N, q, v, Jc, normals, height, mu, f_gr, contact, gap, st)
-                             : ground_force_impl<float>(s, N, q, v, Jc, normals, height, mu, f_gr, contact, gap, st);
-}
-
-template <class T>
-static int integrate_ground_impl(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
-                                 const void* normals, const void* height, const void* mu, const void* tau_ext, void* f_gr, int* contact, void* gap,
-                                 hipStream_t st) {
-  GroundIntegrateArgs<T> a;
-  integrate_args<T>(a, s, N, q, v, M, h, Jc, tau, nullptr, tau_ext, nullptr);   // (zeroes the IntegrateArgs part; f is not read)
-  ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
-  LaunchCtx L; L.st = st;
-  hipError_t e = k_ground_integrate<T>(L, dev_model<T>(s), a);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("integrate ground launch: ") + hipGetErrorString(e));
-  return WBC_OK;
+  return launch_batch(s, N, stream, "ground force", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GroundArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.Jc = (const T*)Jc; a.jpack = s->jpack;
+    ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
+    return k_ground_force<T>(L, dev_model<T>(s), a);
+  });
 }
 
 extern "C" int wbc_integrate_ground_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
@@ -1664,11 +1586,13 @@ extern "C" int wbc_integrate_ground_batch(wbc_solver* s, size_t N, void* q, void
   if (!s) return fail(WBC_E_INVALID, "null solver");
   if (N == 0) return WBC_OK;
   if (!q || !v || !M || !h || !Jc || !tau || !normals || !height || !mu || !f_gr) return fail(WBC_E_INVALID, "null argument");
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? integrate_ground_impl<double>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, f_gr, contact, gap, st)
-                             : integrate_ground_impl<float>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, f_gr, contact, gap, st);
+  return launch_batch(s, N, stream, "integrate ground", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GroundIntegrateArgs<T> a;
+    integrate_args<T>(a, s, N, q, v, M, h, Jc, tau, nullptr, tau_ext, nullptr);   // (zeroes the IntegrateArgs part; f is not read)
+    ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
+    return k_ground_integrate<T>(L, dev_model<T>(s), a);
+  });
 }
 
 // ---- stiction on the ground plant: the anchor spring's stiffness, the law alone, the law + forward dynamics as one launch
@@ -1692,45 +1616,21 @@ static void stick_io(StickIO<T>& k, const wbc_solver* s, void* anchor, int* stic
   k.anchor = (T*)anchor; k.stick = stick; k.k_t = (T)s->stiction.k_t;
 }
 
-template <class T>
-static int ground_stick_force_impl(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals, const void* height,
-                                   const void* mu, void* anchor, int* stick, void* f_gr, int* contact, void* gap, hipStream_t st) {
-  StickArgs<T> a;
-  std::memset(&a, 0, sizeof(a));
-  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.Jc = (const T*)Jc; a.jpack = s->jpack;
-  ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
-  stick_io(a.s, s, anchor, stick);
-  LaunchCtx L; L.st = st;
-  hipError_t e = k_stick_force<T>(L, dev_model<T>(s), a);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("ground stick force launch: ") + hipGetErrorString(e));
-  return WBC_OK;
-}
-
 extern "C" int wbc_ground_stick_force_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* Jc, const void* normals,
                                             const void* height, const void* mu, void* anchor, int* stick, void* f_gr, int* contact, void* gap,
                                             void* stream) {
   if (!s) return fail(WBC_E_INVALID, "null solver");
   if (N == 0) return WBC_OK;
   if (!q || !v || !Jc || !normals || !height || !mu || !anchor || !stick || !f_gr) return fail(WBC_E_INVALID, "null argument");
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64 ? ground_stick_force_impl<double>(s, N, q, v, Jc, normals, height, mu, anchor, stick, f_gr, contact, gap, st)
-                             : ground_stick_force_impl<float>(s, N, q, v, Jc, normals, height, mu, anchor, stick, f_gr, contact, gap, st);
-}
-
-template <class T>
-static int integrate_ground_stick_impl(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc, const void* tau,
-                                       const void* normals, const void* height, const void* mu, const void* tau_ext, void* anchor, int* stick,
-                                       void* f_gr, int* contact, void* gap, hipStream_t st) {
-  StickIntegrateArgs<T> a;
-  integrate_args<T>(a, s, N, q, v, M, h, Jc, tau, nullptr, tau_ext, nullptr);   // (zeroes the IntegrateArgs part; f is not read)
-  ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
-  stick_io(a.s, s, anchor, stick);
-  LaunchCtx L; L.st = st;
-  hipError_t e = k_stick_integrate<T>(L, dev_model<T>(s), a);
-  if (e != hipSuccess) return fail(WBC_E_HIP, std::string("integrate ground stick launch: ") + hipGetErrorString(e));
-  return WBC_OK;
+  return launch_batch(s, N, stream, "ground stick force", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    StickArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.Jc = (const T*)Jc; a.jpack = s->jpack;
+    ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
+    stick_io(a.s, s, anchor, stick);
+    return k_stick_force<T>(L, dev_model<T>(s), a);
+  });
 }
 
 extern "C" int wbc_integrate_ground_stick_batch(wbc_solver* s, size_t N, void* q, void* v, const void* M, const void* h, const void* Jc,
@@ -1739,12 +1639,14 @@ extern "C" int wbc_integrate_ground_stick_batch(wbc_solver* s, size_t N, void* q
   if (!s) return fail(WBC_E_INVALID, "null solver");
   if (N == 0) return WBC_OK;
   if (!q || !v || !M || !h || !Jc || !tau || !normals || !height || !mu || !anchor || !stick || !f_gr) return fail(WBC_E_INVALID, "null argument");
-  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
-  ON_DEVICE(s);
-  hipStream_t st = (hipStream_t)stream;
-  return s->dtype == WBC_F64
-             ? integrate_ground_stick_impl<double>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, anchor, stick, f_gr, contact, gap, st)
-             : integrate_ground_stick_impl<float>(s, N, q, v, M, h, Jc, tau, normals, height, mu, tau_ext, anchor, stick, f_gr, contact, gap, st);
+  return launch_batch(s, N, stream, "integrate ground stick", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    StickIntegrateArgs<T> a;
+    integrate_args<T>(a, s, N, q, v, M, h, Jc, tau, nullptr, tau_ext, nullptr);   // (zeroes the IntegrateArgs part; f is not read)
+    ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
+    stick_io(a.s, s, anchor, stick);
+    return k_stick_integrate<T>(L, dev_model<T>(s), a);
+  });
 }
 
 // ---- scored rollouts: the weights, the superset rollout, one tick's cost, the per-group selection
