@@ -31,35 +31,26 @@ WBC_DEV void com_reference_body(const DevModel<T>* __restrict__ model, const Dev
     __syncthreads();
   }
   const T* cst = EXT ? cst_ext : cst_own;
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
+  WBC_LAUNDERED_TID(tx);
   const size_t N = a.N;
-  const unsigned N32 = (unsigned)N;
-  const int leg = (int)((tx & 63) >> 4);
-  const size_t s_raw = (size_t)blockIdx.x * SPW + (tx & 15);
-  const bool slot_ok = SPW == 16 || (int)(tx & 15) < SPW;   // (SPW <= 16 states per workgroup, see WBC_ADDR_MACROS)
-  const bool live = slot_ok && s_raw < N;
-  const unsigned s32 = (unsigned)(live ? s_raw : (slot_ok ? N - 1 : (size_t)blockIdx.x * SPW));
-#define RCS(i) cst[(i) * 4 + leg]
-#define RLDU(ptr, comp) (*(const T*)((const char*)((ptr) + (size_t)(comp) * N) + (size_t)(s32 * (unsigned)sizeof(T))))
-#define RLDV(ptr, comp) (*(const T*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))))
-#define RSTV(ptr, comp, val) do { if (live) *(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)
+  WBC_LEG_LANE(SPW, 1, WBC_SRAW_A(SPW))   // (SPW <= 16 states per workgroup: lane_rows.hip.hpp)
+  using RowV = T;
   static_assert(!SIMG || EXT, "the LDS images belong to the rollout kernel's roles");   // (the state from the workgroup's LDS image: WBC_STATE_MACROS, dyn_split.hip.hpp)
   const T* const si_ = SIMG ? a.simg + (int)(s32 - (unsigned)((size_t)blockIdx.x * SPW)) : nullptr;
   T qb[7], vb[6], pl[PLAN_WORDS];
 #pragma unroll
-  for (int c = 0; c < 7; ++c) qb[c] = SIMG ? si_[c * 16] : RLDU(a.q, c);
+  for (int c = 0; c < 7; ++c) qb[c] = SIMG ? si_[c * 16] : LDU(a.q, c);
 #pragma unroll
-  for (int c = 0; c < 6; ++c) vb[c] = SIMG ? si_[(SIMG_V + c) * 16] : RLDU(a.v, c);
+  for (int c = 0; c < 6; ++c) vb[c] = SIMG ? si_[(SIMG_V + c) * 16] : LDU(a.v, c);
 #pragma unroll
-  for (int c = 0; c < PLAN_WORDS; ++c) pl[c] = SIMG ? a.planimg[c * 16 + (si_ - a.simg)] : RLDU(a.plan, c);
+  for (int c = 0; c < PLAN_WORDS; ++c) pl[c] = SIMG ? a.planimg[c * 16 + (si_ - a.simg)] : LDU(a.plan, c);
   int jx[3];
   jidx_of_leg(model, a.jpack, leg, jx);
   T ql[3], vl[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    ql[k] = SIMG ? si_[(7 + jx[k]) * 16] : RLDV(a.q, 7 + jx[k]);
-    vl[k] = SIMG ? si_[(SIMG_V + 6 + jx[k]) * 16] : RLDV(a.v, 6 + jx[k]);
+    ql[k] = SIMG ? si_[(7 + jx[k]) * 16] : LDV(a.q, 7 + jx[k]);
+    vl[k] = SIMG ? si_[(SIMG_V + 6 + jx[k]) * 16] : LDV(a.v, 6 + jx[k]);
   }
   T qx, qy, qz, qw;
   {
@@ -86,10 +77,10 @@ WBC_DEV void com_reference_body(const DevModel<T>* __restrict__ model, const Dev
     T sn, cs;
     sincos_t(ql[k], &sn, &cs);
 #pragma unroll
-    for (int e = 0; e < 9; ++e) E[k].a[e] = RCS(o + e) + cs * RCS(o + 9 + e) + sn * RCS(o + 18 + e);
-    const V3<T> r = mk<T>(RCS(o + 27), RCS(o + 28), RCS(o + 29));
-    const V3<T> ax = mk<T>(RCS(o + 30), RCS(o + 31), RCS(o + 32));
-    const V3<T> h = mk<T>(RCS(o + 34), RCS(o + 35), RCS(o + 36));
+    for (int e = 0; e < 9; ++e) E[k].a[e] = CS(o + e) + cs * CS(o + 9 + e) + sn * CS(o + 18 + e);
+    const V3<T> r = mk<T>(CS(o + 27), CS(o + 28), CS(o + 29));
+    const V3<T> ax = mk<T>(CS(o + 30), CS(o + 31), CS(o + 32));
+    const V3<T> h = mk<T>(CS(o + 34), CS(o + 35), CS(o + 36));
     // E^T omp + ax qdot with every fused multiply-add WRITTEN: left to the compiler, com_reference_kernel and com_swing_reference_kernel contracted this
     // sum differently, and with joint axes off the coordinate axes (ax qdot no longer exact) the fused call's w_des, com and base rows lost the
     // bit-identity with wbc_reference_batch that include/wbc_hip.h promises (tests/test_gpu_variants.py)
@@ -108,23 +99,23 @@ WBC_DEV void com_reference_body(const DevModel<T>* __restrict__ model, const Dev
                  fma_w(ax.z, vl[k], fma_w(e.a[8], omp.z, fma_w(e.a[2], omp.x, e.a[5] * omp.y))));
     }
     const V3<T> vv = tmul(E[k], vp + cross(omp, r));
-    pk[k] = vv * RCS(o + 33) + cross(om, h);
+    pk[k] = vv * CS(o + 33) + cross(om, h);
     omp = om; vp = vv;
   }
   // return sweep: first moment (cm, ch) and linear momentum P of the leg, expressed in the base frame at the end
-  T cm = RCS(2 * JOINT_WORDS + 33);
-  V3<T> ch = mk<T>(RCS(2 * JOINT_WORDS + 34), RCS(2 * JOINT_WORDS + 35), RCS(2 * JOINT_WORDS + 36));
+  T cm = CS(2 * JOINT_WORDS + 33);
+  V3<T> ch = mk<T>(CS(2 * JOINT_WORDS + 34), CS(2 * JOINT_WORDS + 35), CS(2 * JOINT_WORDS + 36));
   V3<T> P = pk[2];
 #pragma unroll
   for (int k = 2; k >= 0; --k) {
     const int o = JOINT_WORDS * k;
-    const V3<T> r = mk<T>(RCS(o + 27), RCS(o + 28), RCS(o + 29));
+    const V3<T> r = mk<T>(CS(o + 27), CS(o + 28), CS(o + 29));
     ch = mul(E[k], ch) + r * cm;       // now in the parent's frame
     P = mul(E[k], P);
     if (k > 0) {
       const int op = JOINT_WORDS * (k - 1);
-      cm += RCS(op + 33);
-      ch = ch + mk<T>(RCS(op + 34), RCS(op + 35), RCS(op + 36));
+      cm += CS(op + 33);
+      ch = ch + mk<T>(CS(op + 34), CS(op + 35), CS(op + 36));
       P = P + pk[k - 1];
     }
   }
@@ -191,21 +182,17 @@ WBC_DEV void com_reference_body(const DevModel<T>* __restrict__ model, const Dev
     to_mem = a.skip_out == 0;
   }
   if (to_mem) {
-    RSTV(a.w_des, sel4<int>(leg, 0, 1, 2, 3), sel4<T>(leg, F.x, F.y, F.z, Mo.x));
-    if (leg < 2) RSTV(a.w_des, 4 + leg, leg == 0 ? Mo.y : Mo.z);
-    RSTV(a.vdot_des, sel4<int>(leg, 0, 1, 2, 3), sel4<T>(leg, acmd[0], acmd[1], acmd[2], alcmd[0]));
-    if (leg >= 2) RSTV(a.vdot_des, 2 + leg, leg == 2 ? alcmd[1] : alcmd[2]);
+    if (live) ROWV(a.w_des, sel4<int>(leg, 0, 1, 2, 3)) = sel4<T>(leg, F.x, F.y, F.z, Mo.x);
+    if (leg < 2) if (live) ROWV(a.w_des, 4 + leg) = leg == 0 ? Mo.y : Mo.z;
+    if (live) ROWV(a.vdot_des, sel4<int>(leg, 0, 1, 2, 3)) = sel4<T>(leg, acmd[0], acmd[1], acmd[2], alcmd[0]);
+    if (leg >= 2) if (live) ROWV(a.vdot_des, 2 + leg) = leg == 2 ? alcmd[1] : alcmd[2];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) RSTV(a.vdot_des, 6 + jx[k], adj[k]);
+    for (int k = 0; k < 3; ++k) if (live) ROWV(a.vdot_des, 6 + jx[k]) = adj[k];
   }
   if (a.com) {
-    RSTV(a.com, sel4<int>(leg, 0, 1, 2, 3), sel4<T>(leg, c.x, c.y, c.z, cd.x));
-    if (leg < 2) RSTV(a.com, 4 + leg, leg == 0 ? cd.y : cd.z);
+    if (live) ROWV(a.com, sel4<int>(leg, 0, 1, 2, 3)) = sel4<T>(leg, c.x, c.y, c.z, cd.x);
+    if (leg < 2) if (live) ROWV(a.com, 4 + leg) = leg == 0 ? cd.y : cd.z;
   }
-#undef RSTV
-#undef RLDV
-#undef RLDU
-#undef RCS
 }
 
 template <class T>

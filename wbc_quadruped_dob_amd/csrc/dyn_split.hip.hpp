@@ -29,22 +29,12 @@
 namespace wbc {
 
 
-// The work-item id passes through an empty asm at the top of every body: inside the persistent rollout kernel the bodies
-// sit in the horizon loop, and without this every lane-derived predicate, LDS address and table index (hundreds of
-// registers' worth) is hoisted out of that loop as "invariant" and spilled.  One no-op per call elsewhere.
-#define WBC_LAUNDERED_TID(name) unsigned name = threadIdx.x; asm volatile("" : "+v"(name))
-#define WBC_ADDR_MACROS                                                                                                   \
+// the lane mapping of a body with EXT / SPW / BLOCK (roles own SPW <= 16 consecutive states; stand-alone kernels run BLOCK / 64 wavefronts) and what its
+// lanes load and store, for the address forms of lane_rows.hip.hpp.  tx: the body's laundered work-item id; a: its SweepArgs.
+#define WBC_ROLE_LANE                                                                                                       \
   const size_t N = a.N;                                                                                                    \
-  const unsigned N32 = (unsigned)N;                                                                                        \
-  /* lane = 16*leg + (state within the wave), as in dyn_sweep_kernel */                                                    \
-  const int leg = (int)((tx & 63) >> 4);                                                                          \
-  /* roles (EXT != 0): a workgroup owns SPW <= 16 consecutive states; lanes of the other slots repeat its first state */   \
-  const size_t s_raw = EXT ? (size_t)blockIdx.x * SPW + (tx & 15)                                                 \
-                           : ((size_t)blockIdx.x * (BLOCK / 64) + (tx >> 6)) * 16 + (tx & 15);           \
-  const bool slot_ok = SPW == 16 || (int)(tx & 15) < SPW;                                                                  \
-  const bool live = slot_ok && s_raw < N;                                                                                  \
-  unsigned s32 = (unsigned)(live ? s_raw : (slot_ok ? N - 1 : (size_t)blockIdx.x * SPW));                                  \
-  const unsigned legN = (unsigned)leg * N32;
+  WBC_LEG_LANE(SPW, 1, EXT ? WBC_SRAW_A(SPW) : WBC_SRAW_W(BLOCK, 1, blockIdx.x))                                           \
+  using RowV = T;
 // the state (q, v): from memory, or -- roles of the rollout workgroups that keep their states on chip, EXT = 3 -- from the workgroup's LDS image (device_types.hpp, SIMG_*),
 // indexed by the slot of the state the lane COMPUTES (dead lanes duplicate a state of their own workgroup).  Needs jx / jxN in scope for the joint rows.
 #define WBC_STATE_MACROS                                                                                                                          \
@@ -55,27 +45,13 @@ namespace wbc {
   (void)ldq; (void)ldv;
 #define LDQJ(k_) (SIMG ? si_[(7 + jx[k_]) * 16] : LDX(a.q, 7, jxN[k_]))
 #define LDVJ(k_) (SIMG ? si_[(SIMG_V + 6 + jx[k_]) * 16] : LDX(a.v, 6, jxN[k_]))
-#define CS(i) cst[(i) * 4 + leg]
-#define LDU(ptr, comp) (*(const T*)((const char*)((ptr) + (size_t)(comp) * N) + (size_t)(s32 * (unsigned)sizeof(T))))
-#define LDV(ptr, comp) (*(const T*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))))
-#define LDX(ptr, c0, xN) (*(const T*)((const char*)((ptr) + (size_t)(c0) * N) + (size_t)(((xN) + s32) * (unsigned)sizeof(T))))
-// (pure-output stores keep their `if (live)` guard here: without it the roles save ~1 % in the fused tick but the persistent rollout
-// kernel, which sits at 256 registers, spills -- 19.5 -> 24.0 us per tick, measured)
-// -DWBC_ROLE_UNGUARD=1 (A/B): pure-output stores of the ROLES (EXT != 0) without their guard -- a dead lane of a role duplicates a state of its own wavefront
-#define WBC_ROLE_LIVE ((0 && EXT != 0) || live)
-// (pure outputs: the body names its policy STP; ST_PLAIN keeps the plain assignment as it always stood, so that the code of the kernels that do not opt in
-//  stays what it was -- routed through store_out<ST_PLAIN> the same stores came out of the compiler in another order, rollout kernels included)
-#define WBC_ST(T_, addr, val) do { if constexpr (STP == ST_PLAIN) *(T_*)(addr) = (val); else store_out<STP>((T_*)(addr), (T_)(val)); } while (0)
-#define STV(ptr, comp, val) do { if (WBC_ROLE_LIVE) WBC_ST(T, (char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T)), val); } while (0)
-#define STVG(ptr, comp, val) do { if (live) *(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)   /* in/out state (observer): dead lanes of OTHER wavefronts would race with the live one */
-#define STL(ptr, c0, stride, val) do { if (WBC_ROLE_LIVE) WBC_ST(T, (char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + s32) * (unsigned)sizeof(T)), val); } while (0)
-#define STLX(ptr, c0, stride, xN, val) do { if (WBC_ROLE_LIVE) WBC_ST(T, (char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + (xN) + s32) * (unsigned)sizeof(T)), val); } while (0)
-#define ST4(ptr, c0, v0_, c1, v1_, c2, v2_, c3, v3_) STV(ptr, sel4<int>(leg, c0, c1, c2, c3), sel4<T>(leg, v0_, v1_, v2_, v3_))
-#define ST4G(ptr, c0, v0_, c1, v1_, c2, v2_, c3, v3_) STVG(ptr, sel4<int>(leg, c0, c1, c2, c3), sel4<T>(leg, v0_, v1_, v2_, v3_))
-#define MAKE_R(R_, qx, qy, qz, qw) do { const T x = qx, y = qy, z = qz, w = qw; \
-    R_.a[0] = 1 - 2 * (y * y + z * z); R_.a[1] = 2 * (x * y - z * w);     R_.a[2] = 2 * (x * z + y * w); \
-    R_.a[3] = 2 * (x * y + z * w);     R_.a[4] = 1 - 2 * (x * x + z * z); R_.a[5] = 2 * (y * z - x * w); \
-    R_.a[6] = 2 * (x * z - y * w);     R_.a[7] = 2 * (y * z + x * w);     R_.a[8] = 1 - 2 * (x * x + y * y); } while (0)
+// Pure-output stores of these bodies are written `if (live) WBC_ST(word, value)`.  The guard stays although a dead lane of a role duplicates a state of
+// its own wavefront: without it the roles save ~1 % in the fused tick but the persistent rollout kernel, which sits at 256 registers, spills --
+// 19.5 -> 24.0 us per tick, measured.  (In/out state -- the observer's -- is stored plainly under `if (live)`: dead lanes of OTHER wavefronts would
+// race with the live one.)
+// WBC_ST: the body names its store policy STP; ST_PLAIN keeps the plain assignment as it always stood, so that the code of the kernels that do not opt in
+// stays what it was -- routed through store_out<ST_PLAIN> the same stores came out of the compiler in another order, rollout kernels included
+#define WBC_ST(word, val) do { if constexpr (STP == ST_PLAIN) (word) = (val); else store_out<STP>(&(word), (std::remove_reference_t<decltype(word)>)(val)); } while (0)
 
 // (A/B) 1: the one-launch tick's rnea role normalises the quaternion with rsqrt_fast: lever arms ~0.2 us earlier
 constexpr int WBC_MJ_WAVES = 2;
@@ -96,11 +72,9 @@ constexpr int WBC_RS_WAVES = 2;
 template <class T, int STP = ST_PLAIN>
 WBC_DEV void structural_consts_quarter(const DevModel<T>* __restrict__ model, const SweepArgs<T>& a, const int* zidx_s, unsigned tx) {
   const size_t N = a.N;
-  const unsigned N32 = (unsigned)N;
-  const int leg = (int)((tx >> 4) & 3), part = (int)(tx >> 6);
-  const size_t s_raw = (size_t)blockIdx.x * 16 + (tx & 15);
-  const bool live = s_raw < N;
-  const unsigned s32 = (unsigned)(live ? s_raw : N - 1);
+  const int part = (int)(tx >> 6);
+  WBC_LEG_LANE(16, 1, WBC_SRAW_A(16))
+  using RowV = T;
   const T Z = (T)0;
   int jq[3];
   jidx_of_leg(model, a.jpack, leg, jq);
@@ -110,42 +84,38 @@ WBC_DEV void structural_consts_quarter(const DevModel<T>* __restrict__ model, co
     // ones, each for both states (as in dyn_sweep_kernel): half the store instructions
     struct alignas(2 * sizeof(T)) T2 { T a, b; };
     const unsigned odd = s32 & 1u, s2 = s32 & ~1u;
-#define ST2C(ptr, comp, val) do { if (live) WBC_ST(T2, (char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s2) * (unsigned)sizeof(T)), (T2{(val), (val)})); } while (0)
     if (part == 3) {
       for (int e = 2 * leg + (int)odd; e < 64; e += 8) {
         const int zi = zidx_s[e];
-        if (zi >= 0) ST2C(a.M, zi, Z);
+        if (zi >= 0) if (live) WBC_ST(ROWV2(T2, a.M, zi, s2), (T2{Z, Z}));
       }
     } else {
       const int mrow = part;
       const int rb = 54 * leg + 18 * mrow;
-      ST2C(a.Jc, rb + (odd ? 1 : 0), ((odd ? 1 : 0) == mrow) ? (T)1 : Z);
-      ST2C(a.Jc, rb + (odd ? 3 + mrow : 2), (!odd && mrow == 2) ? (T)1 : Z);
+      if (live) WBC_ST(ROWV2(T2, a.Jc, rb + (odd ? 1 : 0), s2), (T2{((odd ? 1 : 0) == mrow) ? (T)1 : Z, ((odd ? 1 : 0) == mrow) ? (T)1 : Z}));
+      if (live) WBC_ST(ROWV2(T2, a.Jc, rb + (odd ? 3 + mrow : 2), s2), (T2{(!odd && mrow == 2) ? (T)1 : Z, (!odd && mrow == 2) ? (T)1 : Z}));
 #pragma unroll
       for (int c = 6; c < 18; c += 2) {
         const int col = c + (int)odd - 6;
-        if (col != j0 && col != j1 && col != j2) ST2C(a.Jc, rb + c + (int)odd, Z);
+        if (col != j0 && col != j1 && col != j2) if (live) WBC_ST(ROWV2(T2, a.Jc, rb + c + (int)odd, s2), (T2{Z, Z}));
       }
     }
-#undef ST2C
   } else {
-#define ST1C(ptr, comp, val) do { if (live) WBC_ST(T, (char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T)), val); } while (0)
     if (part == 3) {
       for (int e = leg; e < 64; e += 4) {
         const int zi = zidx_s[e];
-        if (zi >= 0) ST1C(a.M, zi, Z);
+        if (zi >= 0) if (live) WBC_ST(ROWV(a.M, zi), Z);
       }
     } else {
       const int mrow = part;
       const int rb = 54 * leg + 18 * mrow;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) ST1C(a.Jc, rb + c, (c == mrow) ? (T)1 : Z);
-      ST1C(a.Jc, rb + 3 + mrow, Z);
+      for (int c = 0; c < 3; ++c) if (live) WBC_ST(ROWV(a.Jc, rb + c), (c == mrow) ? (T)1 : Z);
+      if (live) WBC_ST(ROWV(a.Jc, rb + 3 + mrow), Z);
 #pragma unroll
       for (int c = 0; c < 12; ++c)
-        if (c != j0 && c != j1 && c != j2) ST1C(a.Jc, rb + 6 + c, Z);
+        if (c != j0 && c != j1 && c != j2) if (live) WBC_ST(ROWV(a.Jc, rb + 6 + c), Z);
     }
-#undef ST1C
   }
 }
 
@@ -174,7 +144,7 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
   }
   const T* cst = EXT ? cst_ext : cst_own;
   const int* zidx_s = EXT ? zidx_ext : zidx_own;
-  WBC_ADDR_MACROS
+  WBC_ROLE_LANE
   WBC_STATE_MACROS
   const bool direct = hand == nullptr;   // (a literal at every call site: folded)
 
@@ -196,16 +166,16 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
     const T Z = (T)0;
     for (int e = leg; e < 64; e += 4) {
       const int zi = zidx_s[e];
-      if (zi >= 0) STV(a.M, zi, Z);
+      if (zi >= 0) if (live) WBC_ST(ROWV(a.M, zi), Z);
     }
 #pragma unroll
     for (int mrow = 0; mrow < 3; ++mrow) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) STL(a.Jc, 18 * mrow + c, 54, (c == mrow) ? (T)1 : Z);
-      STL(a.Jc, 18 * mrow + 3 + mrow, 54, Z);
+      for (int c = 0; c < 3; ++c) if (live) WBC_ST(ROWL(a.Jc, 18 * mrow + c, 54), (c == mrow) ? (T)1 : Z);
+      if (live) WBC_ST(ROWL(a.Jc, 18 * mrow + 3 + mrow, 54), Z);
 #pragma unroll
       for (int c = 0; c < 12; ++c)
-        if (c != jx[0] && c != jx[1] && c != jx[2]) STL(a.Jc, 18 * mrow + 6 + c, 54, Z);   // own-leg columns get data below
+        if (c != jx[0] && c != jx[1] && c != jx[2]) if (live) WBC_ST(ROWL(a.Jc, 18 * mrow + 6 + c, 54), Z);   // own-leg columns get data below
     }
   };
   if constexpr (ZEROS == 1) { if (!a.skip_consts) write_consts(); }
@@ -263,7 +233,7 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
       if (direct) {
         int i = 6 + jx[k], jj = 6 + jx[j];
         if (i > jj) { const int t = i; i = jj; jj = t; }
-        STV(a.M, i * 18 - i * (i - 1) / 2 + (jj - i), mkj);
+        if (live) WBC_ST(ROWV(a.M, i * 18 - i * (i - 1) / 2 + (jj - i)), mkj);
       } else hl[(k * 3 - k * (k - 1) / 2 + (j - k)) * 64] = mkj;
     }
     jc[k] = cross(ax, dft);
@@ -285,7 +255,7 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
     }
   }
   M3<T> R;
-  MAKE_R(R, qx, qy, qz, qw);
+  quat_R(R, qx, qy, qz, qw);
   const V3<T> dw = mul(R, dft);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -293,15 +263,15 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
     const V3<T> jw = mul(R, jc[k]);
     if (direct) {
       const unsigned x = jxN[k];
-      STLX(a.M, 6, 0, x, Mf.x);
-      STLX(a.M, midx18(1, 1) + 5, 0, x, Mf.y);
-      STLX(a.M, midx18(2, 2) + 4, 0, x, Mf.z);
-      STLX(a.M, midx18(3, 3) + 3, 0, x, Mn.x);
-      STLX(a.M, midx18(4, 4) + 2, 0, x, Mn.y);
-      STLX(a.M, midx18(5, 5) + 1, 0, x, Mn.z);
-      STLX(a.Jc, 0 * 18 + 6, 54, x, jw.x);  // overwrites a zero written above (same lane, program order)
-      STLX(a.Jc, 1 * 18 + 6, 54, x, jw.y);
-      STLX(a.Jc, 2 * 18 + 6, 54, x, jw.z);
+      if (live) WBC_ST(ROWLX(a.M, 6, 0, x), Mf.x);
+      if (live) WBC_ST(ROWLX(a.M, midx18(1, 1) + 5, 0, x), Mf.y);
+      if (live) WBC_ST(ROWLX(a.M, midx18(2, 2) + 4, 0, x), Mf.z);
+      if (live) WBC_ST(ROWLX(a.M, midx18(3, 3) + 3, 0, x), Mn.x);
+      if (live) WBC_ST(ROWLX(a.M, midx18(4, 4) + 2, 0, x), Mn.y);
+      if (live) WBC_ST(ROWLX(a.M, midx18(5, 5) + 1, 0, x), Mn.z);
+      if (live) WBC_ST(ROWLX(a.Jc, 0 * 18 + 6, 54, x), jw.x);  // overwrites a zero written above (same lane, program order)
+      if (live) WBC_ST(ROWLX(a.Jc, 1 * 18 + 6, 54, x), jw.y);
+      if (live) WBC_ST(ROWLX(a.Jc, 2 * 18 + 6, 54, x), jw.z);
     } else {
       hl[(6 + 0 + k) * 64] = Mf.x; hl[(6 + 3 + k) * 64] = Mf.y; hl[(6 + 6 + k) * 64] = Mf.z;
       hl[(6 + 9 + k) * 64] = Mn.x; hl[(6 + 12 + k) * 64] = Mn.y; hl[(6 + 15 + k) * 64] = Mn.z;
@@ -309,13 +279,13 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
     }
   }
   if (direct) {
-    STL(a.Jc, 0 * 18 + 4, 54, dw.z);  STL(a.Jc, 0 * 18 + 5, 54, -dw.y);
-    STL(a.Jc, 1 * 18 + 3, 54, -dw.z); STL(a.Jc, 1 * 18 + 5, 54, dw.x);
-    STL(a.Jc, 2 * 18 + 3, 54, dw.y);  STL(a.Jc, 2 * 18 + 4, 54, -dw.x);
+    if (live) WBC_ST(ROWL(a.Jc, 0 * 18 + 4, 54), dw.z);  if (live) WBC_ST(ROWL(a.Jc, 0 * 18 + 5, 54), -dw.y);
+    if (live) WBC_ST(ROWL(a.Jc, 1 * 18 + 3, 54), -dw.z); if (live) WBC_ST(ROWL(a.Jc, 1 * 18 + 5, 54), dw.x);
+    if (live) WBC_ST(ROWL(a.Jc, 2 * 18 + 3, 54), dw.y);  if (live) WBC_ST(ROWL(a.Jc, 2 * 18 + 4, 54), -dw.x);
     if (a.pf) {
-      STL(a.pf, 0, 3, ldq(0) + dw.x);
-      STL(a.pf, 1, 3, ldq(1) + dw.y);
-      STL(a.pf, 2, 3, ldq(2) + dw.z);
+      if (live) WBC_ST(ROWL(a.pf, 0, 3), ldq(0) + dw.x);
+      if (live) WBC_ST(ROWL(a.pf, 1, 3), ldq(1) + dw.y);
+      if (live) WBC_ST(ROWL(a.pf, 2, 3), ldq(2) + dw.z);
     }
   } else {
     hl[33 * 64] = dw.x; hl[34 * 64] = dw.y; hl[35 * 64] = dw.z;
@@ -323,9 +293,9 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
     // integrator's phase 2 (another wavefront) overwrites that image with the NEXT state.  Stored with M and Jc behind the hand-over (rounds 5-6) a stalled store queue let
     // phase 2 win about once in a thousand rollouts: pf = new base position + old lever arm, 4e-4 off (tools/soak.py, seed 101 case 1607; profiles/r06zzz_soak_long.log)
     if (!a.skip_mats && a.pf) {
-      STL(a.pf, 0, 3, ldq(0) + dw.x);
-      STL(a.pf, 1, 3, ldq(1) + dw.y);
-      STL(a.pf, 2, 3, ldq(2) + dw.z);
+      if (live) WBC_ST(ROWL(a.pf, 0, 3), ldq(0) + dw.x);
+      if (live) WBC_ST(ROWL(a.pf, 1, 3), ldq(1) + dw.y);
+      if (live) WBC_ST(ROWL(a.pf, 2, 3), ldq(2) + dw.z);
     }
   }
   {
@@ -340,10 +310,10 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
     const S3<T> Iw = congr(R, tI);
     if (direct) {
       T* M = a.M;
-      ST4(M, midx18(0, 0), tm, midx18(1, 1), tm, midx18(2, 2), tm, midx18(0, 4), hw.z);
-      ST4(M, midx18(0, 5), -hw.y, midx18(1, 3), -hw.z, midx18(1, 5), hw.x, midx18(2, 3), hw.y);
-      ST4(M, midx18(2, 4), -hw.x, midx18(3, 3), Iw.xx, midx18(3, 4), Iw.xy, midx18(3, 5), Iw.xz);
-      if (leg < 3) STV(M, sel4<int>(leg, midx18(4, 4), midx18(4, 5), midx18(5, 5), 0), sel4<T>(leg, Iw.yy, Iw.yz, Iw.zz, Iw.zz));
+      if (live) WBC_ST(ROWV4(M, leg, midx18(0, 0), midx18(1, 1), midx18(2, 2), midx18(0, 4)), sel4<T>(leg, tm, tm, tm, hw.z));
+      if (live) WBC_ST(ROWV4(M, leg, midx18(0, 5), midx18(1, 3), midx18(1, 5), midx18(2, 3)), sel4<T>(leg, -hw.y, -hw.z, hw.x, hw.y));
+      if (live) WBC_ST(ROWV4(M, leg, midx18(2, 4), midx18(3, 3), midx18(3, 4), midx18(3, 5)), sel4<T>(leg, -hw.x, Iw.xx, Iw.xy, Iw.xz));
+      if (leg < 3) if (live) WBC_ST(ROWV(M, sel4<int>(leg, midx18(4, 4), midx18(4, 5), midx18(5, 5), 0)), sel4<T>(leg, Iw.yy, Iw.yz, Iw.zz, Iw.zz));
     } else {
       hl[36 * 64] = tm; hl[37 * 64] = hw.x; hl[38 * 64] = hw.y; hl[39 * 64] = hw.z;
       hl[40 * 64] = Iw.xx; hl[41 * 64] = Iw.xy; hl[42 * 64] = Iw.xz; hl[43 * 64] = Iw.yy; hl[44 * 64] = Iw.yz; hl[45 * 64] = Iw.zz;
@@ -358,29 +328,29 @@ WBC_DEV void mass_jac_body(const DevModel<T>* __restrict__ model, const SweepArg
         for (int j = k; j < 3; ++j) {
           int i = 6 + jx[k], jj = 6 + jx[j];
           if (i > jj) { const int t = i; i = jj; jj = t; }
-          STV(a.M, i * 18 - i * (i - 1) / 2 + (jj - i), hl[(k * 3 - k * (k - 1) / 2 + (j - k)) * 64]);
+          if (live) WBC_ST(ROWV(a.M, i * 18 - i * (i - 1) / 2 + (jj - i)), hl[(k * 3 - k * (k - 1) / 2 + (j - k)) * 64]);
         }
         const unsigned x = jxN[k];
-        STLX(a.M, 6, 0, x, hl[(6 + 0 + k) * 64]);
-        STLX(a.M, midx18(1, 1) + 5, 0, x, hl[(6 + 3 + k) * 64]);
-        STLX(a.M, midx18(2, 2) + 4, 0, x, hl[(6 + 6 + k) * 64]);
-        STLX(a.M, midx18(3, 3) + 3, 0, x, hl[(6 + 9 + k) * 64]);
-        STLX(a.M, midx18(4, 4) + 2, 0, x, hl[(6 + 12 + k) * 64]);
-        STLX(a.M, midx18(5, 5) + 1, 0, x, hl[(6 + 15 + k) * 64]);
-        STLX(a.Jc, 0 * 18 + 6, 54, x, hl[(24 + 0 + k) * 64]);
-        STLX(a.Jc, 1 * 18 + 6, 54, x, hl[(24 + 3 + k) * 64]);
-        STLX(a.Jc, 2 * 18 + 6, 54, x, hl[(24 + 6 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.M, 6, 0, x), hl[(6 + 0 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.M, midx18(1, 1) + 5, 0, x), hl[(6 + 3 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.M, midx18(2, 2) + 4, 0, x), hl[(6 + 6 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.M, midx18(3, 3) + 3, 0, x), hl[(6 + 9 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.M, midx18(4, 4) + 2, 0, x), hl[(6 + 12 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.M, midx18(5, 5) + 1, 0, x), hl[(6 + 15 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.Jc, 0 * 18 + 6, 54, x), hl[(24 + 0 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.Jc, 1 * 18 + 6, 54, x), hl[(24 + 3 + k) * 64]);
+        if (live) WBC_ST(ROWLX(a.Jc, 2 * 18 + 6, 54, x), hl[(24 + 6 + k) * 64]);
       }
       const T dx = hl[33 * 64], dy = hl[34 * 64], dz = hl[35 * 64];
-      STL(a.Jc, 0 * 18 + 4, 54, dz);  STL(a.Jc, 0 * 18 + 5, 54, -dy);
-      STL(a.Jc, 1 * 18 + 3, 54, -dz); STL(a.Jc, 1 * 18 + 5, 54, dx);
-      STL(a.Jc, 2 * 18 + 3, 54, dy);  STL(a.Jc, 2 * 18 + 4, 54, -dx);
+      if (live) WBC_ST(ROWL(a.Jc, 0 * 18 + 4, 54), dz);  if (live) WBC_ST(ROWL(a.Jc, 0 * 18 + 5, 54), -dy);
+      if (live) WBC_ST(ROWL(a.Jc, 1 * 18 + 3, 54), -dz); if (live) WBC_ST(ROWL(a.Jc, 1 * 18 + 5, 54), dx);
+      if (live) WBC_ST(ROWL(a.Jc, 2 * 18 + 3, 54), dy);  if (live) WBC_ST(ROWL(a.Jc, 2 * 18 + 4, 54), -dx);
       const T tm = hl[36 * 64], hwx = hl[37 * 64], hwy = hl[38 * 64], hwz = hl[39 * 64];
       T* M = a.M;
-      ST4(M, midx18(0, 0), tm, midx18(1, 1), tm, midx18(2, 2), tm, midx18(0, 4), hwz);
-      ST4(M, midx18(0, 5), -hwy, midx18(1, 3), -hwz, midx18(1, 5), hwx, midx18(2, 3), hwy);
-      ST4(M, midx18(2, 4), -hwx, midx18(3, 3), hl[40 * 64], midx18(3, 4), hl[41 * 64], midx18(3, 5), hl[42 * 64]);
-      if (leg < 3) STV(M, sel4<int>(leg, midx18(4, 4), midx18(4, 5), midx18(5, 5), 0), sel4<T>(leg, hl[43 * 64], hl[44 * 64], hl[45 * 64], hl[45 * 64]));
+      if (live) WBC_ST(ROWV4(M, leg, midx18(0, 0), midx18(1, 1), midx18(2, 2), midx18(0, 4)), sel4<T>(leg, tm, tm, tm, hwz));
+      if (live) WBC_ST(ROWV4(M, leg, midx18(0, 5), midx18(1, 3), midx18(1, 5), midx18(2, 3)), sel4<T>(leg, -hwy, -hwz, hwx, hwy));
+      if (live) WBC_ST(ROWV4(M, leg, midx18(2, 4), midx18(3, 3), midx18(3, 4), midx18(3, 5)), sel4<T>(leg, -hwx, hl[40 * 64], hl[41 * 64], hl[42 * 64]));
+      if (leg < 3) if (live) WBC_ST(ROWV(M, sel4<int>(leg, midx18(4, 4), midx18(4, 5), midx18(5, 5), 0)), sel4<T>(leg, hl[43 * 64], hl[44 * 64], hl[45 * 64], hl[45 * 64]));
     }
   }
   if constexpr (ZEROS == 2) { if (!a.skip_consts) write_consts(); }   // (own-leg columns were written above: the constants never overlap them)
@@ -429,13 +399,13 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
     __syncthreads();
   }
   const T* cst = EXT ? cst_ext : cst_own;
-  WBC_ADDR_MACROS
+  WBC_ROLE_LANE
   // RS_LANE2: slots 4 .. 7 are the acceleration-only recursion of states 0 .. 3 (they stay !live: they store nothing to memory)
   const bool chainB = LANE2 && (int)(tx & 15) >= SPW && (int)(tx & 15) < 2 * SPW;
   if constexpr (LANE2) {
     if (chainB) { const size_t sb = (size_t)blockIdx.x * SPW + (tx & 15) - SPW; s32 = (unsigned)(sb < N ? sb : N - 1); }
   }
-#define WSTV(comp, val) do { if constexpr (EXT != 0) wsl[(comp) * 16 + (int)(tx & 15)] = (val); else STV(a.ws, comp, val); } while (0)
+#define WSTV(comp, val) do { if constexpr (EXT != 0) wsl[(comp) * 16 + (int)(tx & 15)] = (val); else { if (live) WBC_ST(ROWV(a.ws, comp), val); } } while (0)
 #define WST4(c0, v0_, c1, v1_, c2, v2_, c3, v3_) WSTV(sel4<int>(leg, c0, c1, c2, c3), sel4<T>(leg, v0_, v1_, v2_, v3_))
 #define WSTL(c0, stride, val) WSTV((c0) + (stride) * leg, val)
 
@@ -525,7 +495,7 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
       d = mk<T>(CS(o + 27), CS(o + 28), CS(o + 29)) + mul(E, d);
     }
     M3<T> R0;
-    MAKE_R(R0, qx, qy, qz, qw);
+    quat_R(R0, qx, qy, qz, qw);
     const V3<T> dw0 = mul(R0, d);
     WSTL(WS_D + 0, 3, dw0.x);
     WSTL(WS_D + 1, 3, dw0.y);
@@ -554,7 +524,7 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
   V3<T> omp, vp, aAp, aLp, gLp, a2Ap, a2Lp;
   {
     M3<T> R;
-    MAKE_R(R, qx, qy, qz, qw);
+    quat_R(R, qx, qy, qz, qw);
     const V3<T> om0 = tmul(R, mk<T>(vb[3], vb[4], vb[5]));
     const V3<T> v0 = tmul(R, mk<T>(vb[0], vb[1], vb[2]));
     V3<T> gneg = tmul(R, mk<T>(-model->grav[0], -model->grav[1], -model->grav[2]));
@@ -695,7 +665,7 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
         asm volatile("" : "+s"(jp));
         const unsigned jx_k = ((unsigned)(jp >> (12 * leg)) >> (4 * k)) & 15u;
         const unsigned jxN_k = jx_k * N32;
-        if (h_mem) STLX(a.h, 6, 0, jxN_k, hk);
+        if (h_mem) if (live) WBC_ST(ROWLX(a.h, 6, 0, jxN_k), hk);
         if (hres) hres[(6 + (int)jx_k) * 16 + (int)(tx & 15)] = hk;
       }
       if (STEP) taup[k] = hk + (TWO ? dot(ax, fak.n) : (T)0);
@@ -717,7 +687,7 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
   }
 
   M3<T> R;
-  MAKE_R(R, qx, qy, qz, qw);
+  quat_R(R, qx, qy, qz, qw);
   V3<T> dw = mk<T>(0, 0, 0), jw[3];
   if (GEOM) {
     dw = mul(R, dft);
@@ -725,9 +695,9 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
     for (int k = 0; k < 3; ++k) jw[k] = mul(R, jc[k]);
   }
   if (WPF && a.pf) {
-    STL(a.pf, 0, 3, qpos[0] + dw.x);
-    STL(a.pf, 1, 3, qpos[1] + dw.y);
-    STL(a.pf, 2, 3, qpos[2] + dw.z);
+    if (live) WBC_ST(ROWL(a.pf, 0, 3), qpos[0] + dw.x);
+    if (live) WBC_ST(ROWL(a.pf, 1, 3), qpos[1] + dw.y);
+    if (live) WBC_ST(ROWL(a.pf, 2, 3), qpos[2] + dw.z);
   }
   if (STEP) {
     if constexpr (!EARLY) {
@@ -760,8 +730,8 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
     const V3<T> bff = xrow_sum(facc.f) + mk<T>(pb[BLOCK * 3], pb[BLOCK * 4], pb[BLOCK * 5]);
     const V3<T> hb_f = mul(R, bff), hb_n = mul(R, bfn);
     if (h_mem) {
-      ST4(a.h, 0, hb_f.x, 1, hb_f.y, 2, hb_f.z, 3, hb_n.x);
-      if (leg < 2) STV(a.h, 4 + leg, leg == 0 ? hb_n.y : hb_n.z);
+      if (live) WBC_ST(ROWV4(a.h, leg, 0, 1, 2, 3), sel4<T>(leg, hb_f.x, hb_f.y, hb_f.z, hb_n.x));
+      if (leg < 2) if (live) WBC_ST(ROWV(a.h, 4 + leg), leg == 0 ? hb_n.y : hb_n.z);
     }
     if (hres) {
       hres[sel4<int>(leg, 0, 1, 2, 3) * 16 + (int)(tx & 15)] = sel4<T>(leg, hb_f.x, hb_f.y, hb_f.z, hb_n.x);
@@ -785,16 +755,16 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
 #pragma unroll
     for (int k = 0; k < 3; ++k) beta_l[k] = ct_leg[k] - g_leg[k];
     if (a.p) {
-      ST4(a.p, 0, p_b[0], 1, p_b[1], 2, p_b[2], 3, p_b[3]);
-      if (leg < 2) STV(a.p, 4 + leg, leg == 0 ? p_b[4] : p_b[5]);
+      if (live) WBC_ST(ROWV4(a.p, leg, 0, 1, 2, 3), sel4<T>(leg, p_b[0], p_b[1], p_b[2], p_b[3]));
+      if (leg < 2) if (live) WBC_ST(ROWV(a.p, 4 + leg), leg == 0 ? p_b[4] : p_b[5]);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) STLX(a.p, 6, 0, jxN[k], p_leg[k]);
+      for (int k = 0; k < 3; ++k) if (live) WBC_ST(ROWLX(a.p, 6, 0, jxN[k]), p_leg[k]);
     }
     if (a.beta) {
-      ST4(a.beta, 0, beta_b[0], 1, beta_b[1], 2, beta_b[2], 3, beta_b[3]);
-      if (leg < 2) STV(a.beta, 4 + leg, leg == 0 ? beta_b[4] : beta_b[5]);
+      if (live) WBC_ST(ROWV4(a.beta, leg, 0, 1, 2, 3), sel4<T>(leg, beta_b[0], beta_b[1], beta_b[2], beta_b[3]));
+      if (leg < 2) if (live) WBC_ST(ROWV(a.beta, 4 + leg), leg == 0 ? beta_b[4] : beta_b[5]);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) STLX(a.beta, 6, 0, jxN[k], beta_l[k]);
+      for (int k = 0; k < 3; ++k) if (live) WBC_ST(ROWLX(a.beta, 6, 0, jxN[k]), beta_l[k]);
     }
   }
   if (STEP || OBSW) {
@@ -814,10 +784,10 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
         rb[c] = o1 ? prm.K1[c] * e : r0 + dt * prm.K2[c] * (prm.K1[c] * e - r0);
         p_b[c] = ig;
       }
-      ST4G(a.obs_integ, 0, p_b[0], 1, p_b[1], 2, p_b[2], 3, p_b[3]);
-      if (leg < 2) STVG(a.obs_integ, 4 + leg, leg == 0 ? p_b[4] : p_b[5]);
-      ST4G(a.obs_r, 0, rb[0], 1, rb[1], 2, rb[2], 3, rb[3]);
-      if (leg < 2) STVG(a.obs_r, 4 + leg, leg == 0 ? rb[4] : rb[5]);
+      if (live) ROWV4(a.obs_integ, leg, 0, 1, 2, 3) = sel4<T>(leg, p_b[0], p_b[1], p_b[2], p_b[3]);
+      if (leg < 2) if (live) ROWV(a.obs_integ, 4 + leg) = leg == 0 ? p_b[4] : p_b[5];
+      if (live) ROWV4(a.obs_r, leg, 0, 1, 2, 3) = sel4<T>(leg, rb[0], rb[1], rb[2], rb[3]);
+      if (leg < 2) if (live) ROWV(a.obs_r, 4 + leg) = leg == 0 ? rb[4] : rb[5];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const int c = 6 + jx[k];
@@ -831,8 +801,8 @@ WBC_DEV void rnea_step_body(const DevModel<T>* __restrict__ model, const DevPara
 #pragma unroll
         for (int j = 1; j < 12; ++j) { k1 = (jx[k] == j) ? prm.K1[6 + j] : k1; k2 = (jx[k] == j) ? prm.K2[6 + j] : k2; }
         rl[k] = o1 ? k1 * e : r0 + dt * k2 * (k1 * e - r0);
-        STVG(a.obs_integ, c, ig);
-        STVG(a.obs_r, c, rl[k]);
+        if (live) ROWV(a.obs_integ, c) = ig;
+        if (live) ROWV(a.obs_r, c) = rl[k];
       }
     }
     if constexpr (OBSW) {   // hand rhat to the QP waves, which subtract it from b and tau_partial themselves
@@ -869,18 +839,5 @@ __global__ __launch_bounds__(BLOCK, WBC_RS_WAVES) void rnea_step_kernel(const De
   if (a.qp_todo && blockIdx.x == 0 && threadIdx.x == 0) a.qp_todo[0] = 0;
   rnea_step_body<T, MODE, BLOCK, 0>(model, prm, a, nullptr, nullptr);
 }
-
-#undef MAKE_R
-#undef ST4
-#undef ST4G
-#undef STVG
-#undef STLX
-#undef STL
-#undef STV
-#undef WBC_ST
-#undef LDX
-#undef LDV
-#undef LDU
-#undef CS
 
 }  // namespace wbc

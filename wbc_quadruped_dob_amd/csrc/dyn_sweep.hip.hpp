@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_types.hpp"
+#include "lane_rows.hip.hpp"
 
 namespace wbc {
 
@@ -39,6 +40,12 @@ template <class T> WBC_DEV V3<T> mul(const M3<T>& m, V3<T> v) {
 template <class T> WBC_DEV V3<T> tmul(const M3<T>& m, V3<T> v) {  // m^T v
   return mk<T>(m.a[0] * v.x + m.a[3] * v.y + m.a[6] * v.z, m.a[1] * v.x + m.a[4] * v.y + m.a[7] * v.z,
                m.a[2] * v.x + m.a[5] * v.y + m.a[8] * v.z);
+}
+// rotation of the unit quaternion (x, y, z, w)
+template <class T> WBC_DEV void quat_R(M3<T>& R, const T x, const T y, const T z, const T w) {
+  R.a[0] = 1 - 2 * (y * y + z * z); R.a[1] = 2 * (x * y - z * w);     R.a[2] = 2 * (x * z + y * w);
+  R.a[3] = 2 * (x * y + z * w);     R.a[4] = 1 - 2 * (x * x + z * z); R.a[5] = 2 * (y * z - x * w);
+  R.a[6] = 2 * (x * z - y * w);     R.a[7] = 2 * (y * z + x * w);     R.a[8] = 1 - 2 * (x * x + y * y);
 }
 // symmetric 3x3: xx,xy,xz,yy,yz,zz
 template <class T> struct S3 { T xx, xy, xz, yy, yz, zz; };
@@ -324,38 +331,20 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
   SSTAMP();  // 0: kernel entry
 
   const size_t N = a.N;
-  const unsigned N32 = (unsigned)N;
-  // lane = 16*leg + (state within the wave): each 16-lane row owns one leg of 16 consecutive states
+  // lane = 16*leg + (state within the wave): each 16-lane row owns one leg of 16 consecutive states (lane_rows.hip.hpp; the id is not laundered here)
   const unsigned tix = threadIdx.x & (unsigned)(BLOCK - 1);   // thread within the BLOCK threads that run this body (a kernel may run several bodies side by side: tile_tick.hip.hpp)
-  const int leg = (int)((tix & 63) >> 4);
-  const size_t s_raw = (((size_t)blk * (BLOCK / 64) + (tix >> 6)) * 16 + (tix & 15)) * W;   // first state of this lane
-  const bool live = s_raw < N;                            // (W = 2: N is even, so both states of a lane are in range together)
+  const unsigned tx = tix;
+  WBC_LEG_LANE(16, W, WBC_SRAW_W(BLOCK, W, blk))
   // Dead lanes (beyond the batch) recompute the last state(s) and STORE what they computed: bit-identical duplicates of the live
   // lane's values at the same addresses.  Guarding every store with `if (live)` made each of the ~100 stores its own exec region
   // (s_and_saveexec / s_cbranch_execz / s_or: ~45 cycles each for a lone wavefront, tools/issue_probe.hip).  Only the observer state,
-  // which is read-modified-written, keeps the guard (STVG): an all-dead wavefront could read it after the live one wrote it.
+  // which is read-modified-written, keeps the guard: an all-dead wavefront could read it after the live one wrote it.
   // (The workspace words that DEPEND on that state -- b = w_des - rhat, tau_partial - rhat -- are stored unguarded too; that is only
   // sound while an observer variant's workgroup is ONE wavefront: static_assert in dyn_sweep_kernel.)
-  const unsigned s32 = (unsigned)(live ? s_raw : N - W);
-  const unsigned legN = (unsigned)leg * N32;
-#define CS(i) cst[(i) * 4 + leg]
-  // Addressing: every array is < 4 GiB (max_batch is capped at create), so a component row is reached as
-  // (uniform 64-bit base in SGPRs) + (32-bit per-lane byte offset): no 64-bit vector address arithmetic.
-  //   LDU/STU: component index is wave-uniform;  LDV/STV: component index differs per lane.
-#define LDU(ptr, comp) (*(const V*)((const char*)((ptr) + (size_t)(comp) * N) + (size_t)(s32 * (unsigned)sizeof(T))))
-#define LDV(ptr, comp) (*(const V*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))))
-#define STU(ptr, comp, val) do { *(V*)((char*)((ptr) + (size_t)(comp) * N) + (size_t)(s32 * (unsigned)sizeof(T))) = (val); } while (0)
-#define STV(ptr, comp, val) do { *(V*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)
-#define STVG(ptr, comp, val) do { if (live) *(V*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)   /* in/out state (observer): dead lanes of OTHER wavefronts would race with the live one */
-  // leg-strided component: comp = c0 + stride*leg (+ per-lane extra element offset xN = x*N)
-#define STL(ptr, c0, stride, val) do { *(V*)((char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + s32) * (unsigned)sizeof(T))) = (val); } while (0)
-#define STLX(ptr, c0, stride, xN, val) do { *(V*)((char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + (xN) + s32) * (unsigned)sizeof(T))) = (val); } while (0)
-  // four base-replicated values, one per lane of the quad
-#define ST4(ptr, c0, v0_, c1, v1_, c2, v2_, c3, v3_) STV(ptr, sel4<int>(leg, c0, c1, c2, c3), sel4<V>(leg, v0_, v1_, v2_, v3_))
-#define ST4G(ptr, c0, v0_, c1, v1_, c2, v2_, c3, v3_) STVG(ptr, sel4<int>(leg, c0, c1, c2, c3), sel4<V>(leg, v0_, v1_, v2_, v3_))
+  using RowV = V;   // LDU / ROWU: component index wave-uniform;  LDV / ROWV: it differs per lane (lane_rows.hip.hpp)
   const int hcol = xr.col0 + (int)(tix & 15) * W;   // (XR) my first state's column of the tile
   (void)hcol;
-#define WSTV(comp, val) do { if constexpr (XR) *(V*)(xr.hand + ((comp) - WS_TAUP + HAND_TAUP) * xr.hs + hcol) = (val); else STV(a.ws, comp, val); } while (0)   /* step workspace */
+#define WSTV(comp, val) do { if constexpr (XR) *(V*)(xr.hand + ((comp) - WS_TAUP + HAND_TAUP) * xr.hs + hcol) = (val); else ROWV(a.ws, comp) = (val); } while (0)   /* step workspace */
 #define WST4(c0, v0_, c1, v1_, c2, v2_, c3, v3_) WSTV(sel4<int>(leg, c0, c1, c2, c3), sel4<V>(leg, v0_, v1_, v2_, v3_))
 #define WSTL(c0, stride, val) WSTV((c0) + (stride) * leg, val)
 
@@ -373,15 +362,15 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
   V ql[3], vl[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    ql[k] = *(const V*)((const char*)(a.q + (size_t)7 * N) + (size_t)((jxN[k] + s32) * (unsigned)sizeof(T)));
-    vl[k] = *(const V*)((const char*)(a.v + (size_t)6 * N) + (size_t)((jxN[k] + s32) * (unsigned)sizeof(T)));
+    ql[k] = LDX(a.q, 7, jxN[k]);
+    vl[k] = LDX(a.v, 6, jxN[k]);
   }
   // desired accelerations: needed in and after the return sweep, requested here (see the parking comment above)
   V al[3] = {0, 0, 0}, ad_in[6] = {0, 0, 0, 0, 0, 0};
   if (STEP) {
 #pragma unroll
     for (int k = 0; k < 3; ++k)
-      al[k] = *(const V*)((const char*)(a.vdot_des + (size_t)6 * N) + (size_t)((jxN[k] + s32) * (unsigned)sizeof(T)));
+      al[k] = LDX(a.vdot_des, 6, jxN[k]);
 #pragma unroll
     for (int c = 0; c < 6; ++c) ad_in[c] = LDU(a.vdot_des, c);
   }
@@ -440,40 +429,40 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
       struct alignas(2 * sizeof(V)) T2 { V a, b; };
       const unsigned odd = (s32 / W) & 1u, s2 = s32 & ~(unsigned)(2 * W - 1);
       // (N is a multiple of 2 W here: the states of a lane pair are in range together, so the pair store needs no guard of its own)
-#define ST2C(ptr, comp, val) do { *(T2*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s2) * (unsigned)sizeof(T))) = T2{(val), (val)}; } while (0)
       for (int e = 2 * leg + (int)odd; e < 64; e += 8) {
         const int zi = zidx_s[e];
-        if (zi >= 0) ST2C(a.M, zi, Z);
+        if (zi >= 0) ROWV2(T2, a.M, zi, s2) = T2{Z, Z};
       }
       // Jc rows of my foot: 16 constant entries per row (identity block, skew diagonal, 12 joint columns), 48 in all
 #pragma unroll
       for (int mrow = 0; mrow < 3; ++mrow) {
         const int rb = 54 * leg + 18 * mrow;
         // pairs (even entry, odd entry): (0,1) (2, 3+mrow) (6,7) (8,9) (10,11) (12,13) (14,15) (16,17)
-        ST2C(a.Jc, rb + (odd ? 1 : 0), ((odd ? 1 : 0) == mrow) ? (T)1 : Z);
-        ST2C(a.Jc, rb + (odd ? 3 + mrow : 2), (!odd && mrow == 2) ? (T)1 : Z);
+        const V i01 = ((odd ? 1 : 0) == mrow) ? (T)1 : Z;
+        ROWV2(T2, a.Jc, rb + (odd ? 1 : 0), s2) = T2{i01, i01};
+        const V i2 = (!odd && mrow == 2) ? (T)1 : Z;
+        ROWV2(T2, a.Jc, rb + (odd ? 3 + mrow : 2), s2) = T2{i2, i2};
         // joint columns: zeros, EXCEPT the three columns of my own leg, which the return sweep writes with data
         // (zero-filling them first cost 9 words/leg = 7 % of the kernel's store bytes, PMC WRITE_SIZE)
 #pragma unroll
         for (int c = 6; c < 18; c += 2) {
           const int col = c + (int)odd - 6;
-          if (col != jx[0] && col != jx[1] && col != jx[2]) ST2C(a.Jc, rb + c + (int)odd, Z);
+          if (col != jx[0] && col != jx[1] && col != jx[2]) ROWV2(T2, a.Jc, rb + c + (int)odd, s2) = T2{Z, Z};
         }
       }
-#undef ST2C
     } else {
       for (int e = leg; e < 64; e += 4) {
         const int zi = zidx_s[e];
-        if (zi >= 0) STV(a.M, zi, Z);
+        if (zi >= 0) ROWV(a.M, zi) = Z;
       }
 #pragma unroll
       for (int mrow = 0; mrow < 3; ++mrow) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) STL(a.Jc, 18 * mrow + c, 54, (c == mrow) ? (T)1 : Z);
-        STL(a.Jc, 18 * mrow + 3 + mrow, 54, Z);
+        for (int c = 0; c < 3; ++c) ROWL(a.Jc, 18 * mrow + c, 54) = (c == mrow) ? (T)1 : Z;
+        ROWL(a.Jc, 18 * mrow + 3 + mrow, 54) = Z;
 #pragma unroll
         for (int c = 0; c < 12; ++c)
-          if (c != jx[0] && c != jx[1] && c != jx[2]) STL(a.Jc, 18 * mrow + 6 + c, 54, Z);
+          if (c != jx[0] && c != jx[1] && c != jx[2]) ROWL(a.Jc, 18 * mrow + 6 + c, 54) = Z;
       }
     }
   }
@@ -484,10 +473,6 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
     const V n = rsqrt_t(qb[3] * qb[3] + qb[4] * qb[4] + qb[5] * qb[5] + qb[6] * qb[6]);
     qx = qb[3] * n; qy = qb[4] * n; qz = qb[5] * n; qw = qb[6] * n;
   }
-#define MAKE_R(R_) do { const V x = qx, y = qy, z = qz, w = qw; \
-    R_.a[0] = 1 - 2 * (y * y + z * z); R_.a[1] = 2 * (x * y - z * w);     R_.a[2] = 2 * (x * z + y * w); \
-    R_.a[3] = 2 * (x * y + z * w);     R_.a[4] = 1 - 2 * (x * x + z * z); R_.a[5] = 2 * (y * z - x * w); \
-    R_.a[6] = 2 * (x * z - y * w);     R_.a[7] = 2 * (y * z + x * w);     R_.a[8] = 1 - 2 * (x * x + y * y); } while (0)
   const V bm = model->base_m;
   const V3<V> bh = mk<V>(model->base_h[0], model->base_h[1], model->base_h[2]);
   S3<V> bI;
@@ -505,7 +490,7 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
   V3<V> omp, vp, aAp, aLp;
   {
     M3<V> R;
-    MAKE_R(R);
+    quat_R(R, qx, qy, qz, qw);
     SF<V> bw;
     const V3<V> om0 = tmul(R, mk<V>(vb[3], vb[4], vb[5]));
     const V3<V> v0 = tmul(R, mk<V>(vb[0], vb[1], vb[2]));
@@ -602,7 +587,7 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
     // RNEA projection on the joint axis
     {
       const V hk = dot(ax, fk.n);
-      if (MATS) STLX(a.h, 6, 0, jxN[k], hk);
+      if (MATS) ROWLX(a.h, 6, 0, jxN[k]) = hk;
       if (STEP) taup[k] += hk;
     }
     // CRBA: close the composite of joint k
@@ -619,7 +604,7 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
       if (MATS) {
         int i = 6 + jx[k], jj = 6 + jx[j];
         if (i > jj) { const int t = i; i = jj; jj = t; }
-        STV(a.M, i * 18 - i * (i - 1) / 2 + (jj - i), mkj);
+        ROWV(a.M, i * 18 - i * (i - 1) / 2 + (jj - i)) = mkj;
       }
       if (STEP) { taup[k] += mkj * al[j]; if (j != k) taup[j] += mkj * al[k]; }
     }
@@ -648,7 +633,7 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
   // now: facc (macc, gacc) = leg wrench at the base, base coords; (cm,ch,cI) = leg composite in base
   // coords; dft = foot relative to base origin in base coords; jc[], Fp[] in base coords.
   M3<V> R;
-  MAKE_R(R);
+  quat_R(R, qx, qy, qz, qw);
   const V3<V> dw = mul(R, dft);
   V3<V> jw[3];
 #pragma unroll
@@ -664,32 +649,32 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
       const V3<V> Mf = mul(R, Fp[k].f), Mn = mul(R, Fp[k].n);  // base-leg column, world axes
       if (MATS) {
         const unsigned x = jxN[k];
-        STLX(a.M, 6, 0, x, Mf.x);                       // midx18(0, 6+j) = 6 + j
-        STLX(a.M, midx18(1, 1) + 5, 0, x, Mf.y);        // midx18(r, 6+j) = midx18(r,r) + 6 - r + j
-        STLX(a.M, midx18(2, 2) + 4, 0, x, Mf.z);
-        STLX(a.M, midx18(3, 3) + 3, 0, x, Mn.x);
-        STLX(a.M, midx18(4, 4) + 2, 0, x, Mn.y);
-        STLX(a.M, midx18(5, 5) + 1, 0, x, Mn.z);
+        ROWLX(a.M, 6, 0, x) = Mf.x;                       // midx18(0, 6+j) = 6 + j
+        ROWLX(a.M, midx18(1, 1) + 5, 0, x) = Mf.y;        // midx18(r, 6+j) = midx18(r,r) + 6 - r + j
+        ROWLX(a.M, midx18(2, 2) + 4, 0, x) = Mf.z;
+        ROWLX(a.M, midx18(3, 3) + 3, 0, x) = Mn.x;
+        ROWLX(a.M, midx18(4, 4) + 2, 0, x) = Mn.y;
+        ROWLX(a.M, midx18(5, 5) + 1, 0, x) = Mn.z;
       }
       if (STEP) taup[k] += Mf.x * ad[0] + Mf.y * ad[1] + Mf.z * ad[2] + Mn.x * ad[3] + Mn.y * ad[4] + Mn.z * ad[5];
     }
   }
   if (MATS) {
     // Jc rows of this lane's foot, (3*leg+m)*18 + c: base rotational block and own-leg columns
-    STL(a.Jc, 0 * 18 + 4, 54, dw.z);  STL(a.Jc, 0 * 18 + 5, 54, -dw.y);
-    STL(a.Jc, 1 * 18 + 3, 54, -dw.z); STL(a.Jc, 1 * 18 + 5, 54, dw.x);
-    STL(a.Jc, 2 * 18 + 3, 54, dw.y);  STL(a.Jc, 2 * 18 + 4, 54, -dw.x);
+    ROWL(a.Jc, 0 * 18 + 4, 54) = dw.z;  ROWL(a.Jc, 0 * 18 + 5, 54) = -dw.y;
+    ROWL(a.Jc, 1 * 18 + 3, 54) = -dw.z; ROWL(a.Jc, 1 * 18 + 5, 54) = dw.x;
+    ROWL(a.Jc, 2 * 18 + 3, 54) = dw.y;  ROWL(a.Jc, 2 * 18 + 4, 54) = -dw.x;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {  // overwrite the zeros written above (same lane, same address: program order)
-      STLX(a.Jc, 0 * 18 + 6, 54, jxN[k], jw[k].x);
-      STLX(a.Jc, 1 * 18 + 6, 54, jxN[k], jw[k].y);
-      STLX(a.Jc, 2 * 18 + 6, 54, jxN[k], jw[k].z);
+      ROWLX(a.Jc, 0 * 18 + 6, 54, jxN[k]) = jw[k].x;
+      ROWLX(a.Jc, 1 * 18 + 6, 54, jxN[k]) = jw[k].y;
+      ROWLX(a.Jc, 2 * 18 + 6, 54, jxN[k]) = jw[k].z;
     }
   }
   if (a.pf) {   // base position: parked at the top of the kernel
-    STL(a.pf, 0, 3, px[BLOCK * 6] + dw.x);
-    STL(a.pf, 1, 3, px[BLOCK * 7] + dw.y);
-    STL(a.pf, 2, 3, px[BLOCK * 8] + dw.z);
+    ROWL(a.pf, 0, 3) = px[BLOCK * 6] + dw.x;
+    ROWL(a.pf, 1, 3) = px[BLOCK * 7] + dw.y;
+    ROWL(a.pf, 2, 3) = px[BLOCK * 8] + dw.z;
   }
   // the QP's geometry (foot lever arms, own-leg Jacobian blocks: 48 of the 66 workspace words) is a subset of Jc; when
   // Jc is being written anyway the QP kernel reads it from there and these stores are skipped (-9 % store bytes)
@@ -715,8 +700,8 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
     const V3<V> bfn = mk<V>(xa[0], xa[1], xa[2]) + mk<V>(pb[0], pb[BLOCK], pb[BLOCK * 2]);   // total bias wrench, base coords
     const V3<V> bff = mk<V>(xa[3], xa[4], xa[5]) + mk<V>(pb[BLOCK * 3], pb[BLOCK * 4], pb[BLOCK * 5]);
     const V3<V> hb_f = mul(R, bff), hb_n = mul(R, bfn);  // h base rows (force, moment), world
-    ST4(a.h, 0, hb_f.x, 1, hb_f.y, 2, hb_f.z, 3, hb_n.x);
-    if (leg < 2) STV(a.h, 4 + leg, leg == 0 ? hb_n.y : hb_n.z);
+    ROWV4(a.h, leg, 0, 1, 2, 3) = sel4<V>(leg, hb_f.x, hb_f.y, hb_f.z, hb_n.x);
+    if (leg < 2) ROWV(a.h, 4 + leg) = leg == 0 ? hb_n.y : hb_n.z;
     const V tm = xa[6] + bm;
     const V3<V> th = mk<V>(xa[7], xa[8], xa[9]) + bh;
     S3<V> tI;
@@ -726,10 +711,10 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
     const S3<V> Iw = congr(R, tI);
     // base 6x6 block: 15 data-dependent entries (the 6 structural zeros went out with the early stores)
     T* M = a.M;
-    ST4(M, midx18(0, 0), tm, midx18(1, 1), tm, midx18(2, 2), tm, midx18(0, 4), hw.z);
-    ST4(M, midx18(0, 5), -hw.y, midx18(1, 3), -hw.z, midx18(1, 5), hw.x, midx18(2, 3), hw.y);
-    ST4(M, midx18(2, 4), -hw.x, midx18(3, 3), Iw.xx, midx18(3, 4), Iw.xy, midx18(3, 5), Iw.xz);
-    if (leg < 3) STV(M, sel4<int>(leg, midx18(4, 4), midx18(4, 5), midx18(5, 5), 0), sel4<V>(leg, Iw.yy, Iw.yz, Iw.zz, Iw.zz));
+    ROWV4(M, leg, midx18(0, 0), midx18(1, 1), midx18(2, 2), midx18(0, 4)) = sel4<V>(leg, tm, tm, tm, hw.z);
+    ROWV4(M, leg, midx18(0, 5), midx18(1, 3), midx18(1, 5), midx18(2, 3)) = sel4<V>(leg, -hw.y, -hw.z, hw.x, hw.y);
+    ROWV4(M, leg, midx18(2, 4), midx18(3, 3), midx18(3, 4), midx18(3, 5)) = sel4<V>(leg, -hw.x, Iw.xx, Iw.xy, Iw.xz);
+    if (leg < 3) ROWV(M, sel4<int>(leg, midx18(4, 4), midx18(4, 5), midx18(5, 5), 0)) = sel4<V>(leg, Iw.yy, Iw.yz, Iw.zz, Iw.zz);
   }
   // ------------------------------------------------------------------ observer: second pass over the leg
   // body momenta I v, gravity-only forces and their leaf->root accumulation (a5): velocities are re-propagated
@@ -820,16 +805,16 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
 #pragma unroll
     for (int k = 0; k < 3; ++k) beta_l[k] = ct_leg[k] - g_leg[k];
     if (a.p) {
-      ST4(a.p, 0, p_b[0], 1, p_b[1], 2, p_b[2], 3, p_b[3]);
-      if (leg < 2) STV(a.p, 4 + leg, leg == 0 ? p_b[4] : p_b[5]);
+      ROWV4(a.p, leg, 0, 1, 2, 3) = sel4<V>(leg, p_b[0], p_b[1], p_b[2], p_b[3]);
+      if (leg < 2) ROWV(a.p, 4 + leg) = leg == 0 ? p_b[4] : p_b[5];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) STLX(a.p, 6, 0, jxN[k], p_leg[k]);
+      for (int k = 0; k < 3; ++k) ROWLX(a.p, 6, 0, jxN[k]) = p_leg[k];
     }
     if (a.beta) {
-      ST4(a.beta, 0, beta_b[0], 1, beta_b[1], 2, beta_b[2], 3, beta_b[3]);
-      if (leg < 2) STV(a.beta, 4 + leg, leg == 0 ? beta_b[4] : beta_b[5]);
+      ROWV4(a.beta, leg, 0, 1, 2, 3) = sel4<V>(leg, beta_b[0], beta_b[1], beta_b[2], beta_b[3]);
+      if (leg < 2) ROWV(a.beta, 4 + leg) = leg == 0 ? beta_b[4] : beta_b[5];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) STLX(a.beta, 6, 0, jxN[k], beta_l[k]);
+      for (int k = 0; k < 3; ++k) ROWLX(a.beta, 6, 0, jxN[k]) = beta_l[k];
     }
   }
 
@@ -853,10 +838,10 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
         p_b[c] = ig;  // reuse as the new integ for the store below
       }
       // (the replicated rows were read by every lane of the wave at the top of the kernel, long before any lane stores to them)
-      ST4G(a.obs_integ, 0, p_b[0], 1, p_b[1], 2, p_b[2], 3, p_b[3]);
-      if (leg < 2) STVG(a.obs_integ, 4 + leg, leg == 0 ? p_b[4] : p_b[5]);
-      ST4G(a.obs_r, 0, rb[0], 1, rb[1], 2, rb[2], 3, rb[3]);
-      if (leg < 2) STVG(a.obs_r, 4 + leg, leg == 0 ? rb[4] : rb[5]);
+      if (live) ROWV4(a.obs_integ, leg, 0, 1, 2, 3) = sel4<V>(leg, p_b[0], p_b[1], p_b[2], p_b[3]);
+      if (leg < 2) if (live) ROWV(a.obs_integ, 4 + leg) = leg == 0 ? p_b[4] : p_b[5];
+      if (live) ROWV4(a.obs_r, leg, 0, 1, 2, 3) = sel4<V>(leg, rb[0], rb[1], rb[2], rb[3]);
+      if (leg < 2) if (live) ROWV(a.obs_r, 4 + leg) = leg == 0 ? rb[4] : rb[5];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const int c = 6 + jx[k];
@@ -865,8 +850,8 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
         const V ig = ob_igl[k] + dt * (u + beta_l[k] + r0);
         const V e = p_leg[k] - ig;
         rl[k] = o1 ? kgain[c] * e : r0 + dt * kgain[18 + c] * (kgain[c] * e - r0);
-        STVG(a.obs_integ, c, ig);
-        STVG(a.obs_r, c, rl[k]);
+        if (live) ROWV(a.obs_integ, c) = ig;
+        if (live) ROWV(a.obs_r, c) = rl[k];
       }
     }
     if (OBS) {
@@ -884,25 +869,14 @@ WBC_DEV void dyn_sweep_body(const DevModel<T>* __restrict__ model, const DevPara
   __builtin_amdgcn_s_waitcnt(0);  // drain: all stores acknowledged
   SSTAMP();  // 10
   if (a.pf && leg < 3)
-    for (int m = 0; m < 3; ++m) STL(a.pf, m, 3, (T)(stp[3 * leg + m + 1] - stp[3 * leg + m]));
-  if (a.pf && leg == 3) STL(a.pf, 0, 3, (T)(stp[10] - stp[9]));
+    for (int m = 0; m < 3; ++m) ROWL(a.pf, m, 3) = (T)(stp[3 * leg + m + 1] - stp[3 * leg + m]);
+  if (a.pf && leg == 3) ROWL(a.pf, 0, 3) = (T)(stp[10] - stp[9]);
 #endif
 #undef SSTAMP
 #undef XSUM
-#undef MAKE_R
 #undef WSTL
 #undef WST4
 #undef WSTV
-#undef ST4
-#undef ST4G
-#undef STVG
-#undef STLX
-#undef STL
-#undef STV
-#undef STU
-#undef LDV
-#undef LDU
-#undef CS
 }
 
 template <class T, int MODE, int BLOCK, int W = 1>

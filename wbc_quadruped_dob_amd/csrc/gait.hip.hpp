@@ -30,29 +30,26 @@ __global__ __launch_bounds__(64) void gait_kernel(const DevModel<T>* __restrict_
   __shared__ T cst[CST_WORDS];
   for (int i = threadIdx.x; i < CST_WORDS; i += blockDim.x) cst[i] = model->cst[i];
   __syncthreads();
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
+  WBC_LAUNDERED_TID(tx);
   const size_t N = a.N;
-  const int leg = (int)((tx & 63) >> 4);
-  const unsigned st = tx & 15;
-  const size_t s_raw = (size_t)blockIdx.x * 16 + st;
-  const bool live = s_raw < N;
-  const unsigned s32 = (unsigned)(live ? s_raw : N - 1);   // lanes beyond the batch recompute its last state and store nothing
-#define RLD(ptr, comp) ((ptr)[(size_t)(comp) * N + s32])
-#define RCS(i) cst[(i) * 4 + leg]
+  const LegLane lane_ = leg_lane<16>(tx, N);   // lanes beyond the batch recompute its last state and store nothing
+  const int leg = lane_.leg;
+  const unsigned st = lane_.st;
+  const bool live = lane_.live;
+  const unsigned s32 = lane_.s32;
   const T phase = a.phase[s32];
   const int prev = a.mask[s32];
   const int sensed = a.contact ? a.contact[s32] : 0;
   T qb[7];
 #pragma unroll
-  for (int c = 0; c < 7; ++c) qb[c] = RLD(a.q, c);
-  const T vx = RLD(a.v, 0), vy = RLD(a.v, 1);
-  const T cvx = RLD(a.cmd, 0), cvy = RLD(a.cmd, 1), wz = RLD(a.cmd, 2), zg = RLD(a.cmd, 3);
+  for (int c = 0; c < 7; ++c) qb[c] = ROWI(a.q, c);
+  const T vx = ROWI(a.v, 0), vy = ROWI(a.v, 1);
+  const T cvx = ROWI(a.cmd, 0), cvy = ROWI(a.cmd, 1), wz = ROWI(a.cmd, 2), zg = ROWI(a.cmd, 3);
   int jx[3];
   jidx_of_leg(model, a.jpack, leg, jx);
   T ql[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) ql[k] = RLD(a.q, 7 + jx[k]);
+  for (int k = 0; k < 3; ++k) ql[k] = ROWI(a.q, 7 + jx[k]);
   M3<T> R;
   {
     const T n = rsqrt_t(qb[3] * qb[3] + qb[4] * qb[4] + qb[5] * qb[5] + qb[6] * qb[6]);
@@ -71,8 +68,8 @@ __global__ __launch_bounds__(64) void gait_kernel(const DevModel<T>* __restrict_
     sincos_t(ql[k], &sn, &cs);
     M3<T> E;
 #pragma unroll
-    for (int e = 0; e < 9; ++e) E.a[e] = RCS(ok + e) + cs * RCS(ok + 9 + e) + sn * RCS(ok + 18 + e);
-    const V3<T> r = mk<T>(RCS(ok + 27), RCS(ok + 28), RCS(ok + 29));
+    for (int e = 0; e < 9; ++e) E.a[e] = CS(ok + e) + cs * CS(ok + 9 + e) + sn * CS(ok + 18 + e);
+    const V3<T> r = mk<T>(CS(ok + 27), CS(ok + 28), CS(ok + 29));
     if (k == 0) {
       o = r;
       A = E;
@@ -86,7 +83,7 @@ __global__ __launch_bounds__(64) void gait_kernel(const DevModel<T>* __restrict_
       A = B;
     }
   }
-  const V3<T> d = o + mul(A, mk<T>(RCS(3 * JOINT_WORDS), RCS(3 * JOINT_WORDS + 1), RCS(3 * JOINT_WORDS + 2)));
+  const V3<T> d = o + mul(A, mk<T>(CS(3 * JOINT_WORDS), CS(3 * JOINT_WORDS + 1), CS(3 * JOINT_WORDS + 2)));
   const V3<T> pf = mk<T>(qb[0], qb[1], qb[2]) + mul(R, d);
 
   // the clock and the schedule: additions, subtractions, comparisons and the one rounded product u
@@ -130,8 +127,6 @@ __global__ __launch_bounds__(64) void gait_kernel(const DevModel<T>* __restrict_
     a.mask[s32] = gait_gather(bm, st);
     if (a.events) a.events[s32] = gait_gather(bl, st) | (gait_gather(bt, st) << 4);
   }
-#undef RCS
-#undef RLD
 }
 
 }  // namespace wbc

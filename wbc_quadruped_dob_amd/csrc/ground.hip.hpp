@@ -29,35 +29,26 @@ namespace wbc {
 WBC_DEV double ground_sqrt(double x) { return sqrt(x); }
 WBC_DEV float ground_sqrt(float x) { return sqrtf(x); }
 
-// where a lane's words lie in the [rows][N] arrays: row `comp` of its state, and row c0 + stride * leg of it (its foot's block of `stride` rows).
-// (An index, not the word: the load stays on the caller's __restrict__ pointer.)
-struct FootAddr {
-  size_t N; unsigned legN, s32;
-  WBC_DEV FootAddr(int leg, unsigned s32_, unsigned N32) : N(N32), legN((unsigned)leg * N32), s32(s32_) {}
-  WBC_DEV size_t row(int comp) const { return (size_t)comp * N + s32; }
-  WBC_DEV size_t leg_row(int c0, int stride) const { return (size_t)c0 * N + (size_t)((unsigned)stride * legN + s32); }
-};
-
 // one lane's foot: returns f_gr, leaves the gap in `phi` and the bit in `touch`.  s32 = the state the lane computes, N32 = the batch size.
 template <class T>
 WBC_DEV V3<T> ground_law(const T* __restrict__ q, const T* __restrict__ v, const T* __restrict__ Jc, const GroundIO<T>& g, unsigned long long jpack,
                          int leg, unsigned s32, unsigned N32, T& phi, bool& touch) {
-  const FootAddr A(leg, s32, N32);
+  const LaneRows A(leg, s32, N32);   // (indices, not words: the loads stay on the __restrict__ pointers)
   int jx[3];
   jidx_of_leg((const DevModel<T>*)nullptr, jpack, leg, jx);
   // the words integrate_body phase 1 loads: the lever arm from the base-angular block -[d]x of my foot's rows, the own-leg Jacobian block
-  const V3<T> dl = mk<T>(Jc[A.leg_row(18 * 1 + 5, 54)], Jc[A.leg_row(18 * 2 + 3, 54)], Jc[A.leg_row(18 * 0 + 4, 54)]);
+  const V3<T> dl = mk<T>(Jc[A.leg_idx(18 * 1 + 5, 54)], Jc[A.leg_idx(18 * 2 + 3, 54)], Jc[A.leg_idx(18 * 0 + 4, 54)]);
   T jcl[3][3], qd[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int col = 6 + jx[k];
-    jcl[0][k] = Jc[A.leg_row(0 + col, 54)]; jcl[1][k] = Jc[A.leg_row(18 + col, 54)]; jcl[2][k] = Jc[A.leg_row(36 + col, 54)];
-    qd[k] = v[A.row(col)];
+    jcl[0][k] = Jc[A.leg_idx(0 + col, 54)]; jcl[1][k] = Jc[A.leg_idx(18 + col, 54)]; jcl[2][k] = Jc[A.leg_idx(36 + col, 54)];
+    qd[k] = v[A.idx(col)];
   }
-  const V3<T> pb = mk<T>(q[A.row(0)], q[A.row(1)], q[A.row(2)]);
-  const V3<T> vb = mk<T>(v[A.row(0)], v[A.row(1)], v[A.row(2)]), om = mk<T>(v[A.row(3)], v[A.row(4)], v[A.row(5)]);
-  const V3<T> n = mk<T>(g.normals[A.leg_row(0, 3)], g.normals[A.leg_row(1, 3)], g.normals[A.leg_row(2, 3)]);
-  const T d = g.height[A.leg_row(0, 1)], mu = g.mu[A.leg_row(0, 1)];
+  const V3<T> pb = mk<T>(q[A.idx(0)], q[A.idx(1)], q[A.idx(2)]);
+  const V3<T> vb = mk<T>(v[A.idx(0)], v[A.idx(1)], v[A.idx(2)]), om = mk<T>(v[A.idx(3)], v[A.idx(4)], v[A.idx(5)]);
+  const V3<T> n = mk<T>(g.normals[A.leg_idx(0, 3)], g.normals[A.leg_idx(1, 3)], g.normals[A.leg_idx(2, 3)]);
+  const T d = g.height[A.leg_idx(0, 1)], mu = g.mu[A.leg_idx(0, 1)];
   const V3<T> pf = pb + dl;
   const V3<T> vf = vb + cross(om, dl) + mk<T>(jcl[0][0] * qd[0] + jcl[0][1] * qd[1] + jcl[0][2] * qd[2],
                                               jcl[1][0] * qd[0] + jcl[1][1] * qd[1] + jcl[1][2] * qd[2],
@@ -90,22 +81,14 @@ WBC_DEV void ground_store(const GroundIO<T>& g, int leg, unsigned st, unsigned s
 
 // the four kernels' lane mapping: lane = 16 * leg + state, one wavefront per workgroup.  Lanes beyond the batch recompute its last state (the state
 // integrate_body gives the same lane) and store nothing.
-struct FootLane { int leg; unsigned st, s32; bool live; };
-WBC_DEV FootLane foot_lane(size_t N) {
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
-  FootLane l;
-  l.leg = (int)((tx & 63) >> 4);
-  l.st = tx & 15;
-  const size_t s_raw = (size_t)blockIdx.x * 16 + l.st;
-  l.live = s_raw < N;
-  l.s32 = (unsigned)(l.live ? s_raw : N - 1);
-  return l;
+WBC_DEV LegLane foot_lane(size_t N) {
+  WBC_LAUNDERED_TID(tx);
+  return leg_lane<16>(tx, N);
 }
 
 template <class T>
 __global__ __launch_bounds__(64) void ground_force_kernel(GroundArgs<T> a) {
-  const FootLane l = foot_lane(a.N);
+  const LegLane l = foot_lane(a.N);
   T phi; bool touch;
   const V3<T> f = ground_law<T>(a.q, a.v, a.Jc, a.g, a.jpack, l.leg, l.s32, (unsigned)a.N, phi, touch);
   ground_store<T>(a.g, l.leg, l.st, l.s32, (unsigned)a.N, l.live, f, phi, touch);
@@ -113,7 +96,7 @@ __global__ __launch_bounds__(64) void ground_force_kernel(GroundArgs<T> a) {
 
 template <class T>
 __global__ __launch_bounds__(64) void ground_integrate_kernel(const DevModel<T>* __restrict__ model, GroundIntegrateArgs<T> a) {
-  const FootLane l = foot_lane(a.N);
+  const LegLane l = foot_lane(a.N);
   T phi; bool touch;
   const V3<T> f = ground_law<T>(a.q, a.v, a.Jc, a.g, a.jpack, l.leg, l.s32, (unsigned)a.N, phi, touch);
   ground_store<T>(a.g, l.leg, l.st, l.s32, (unsigned)a.N, l.live, f, phi, touch);

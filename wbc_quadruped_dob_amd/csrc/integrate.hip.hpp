@@ -121,20 +121,9 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
   const T* const hand = HAND ? hand_ : nullptr;
   const T* const res = RESI ? res_ : nullptr;
   const size_t N = a.N;
-  const unsigned N32 = (unsigned)N;
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
-  const int leg = (int)((tx & 63) >> 4);
-  const size_t s_raw = (size_t)blockIdx.x * SPW + (tx & 15);
-  const bool slot_ok = SPW == 16 || (int)(tx & 15) < SPW;   // (SPW <= 16 states per workgroup, see WBC_ADDR_MACROS)
-  const bool live = slot_ok && s_raw < N;
-  const unsigned s32 = (unsigned)(live ? s_raw : (slot_ok ? N - 1 : (size_t)blockIdx.x * SPW));
-  const unsigned legN = (unsigned)leg * N32;
-#define LDU(ptr, comp) (*(const T*)((const char*)((ptr) + (size_t)(comp) * N) + (size_t)(s32 * (unsigned)sizeof(T))))
-#define LDV(ptr, comp) (*(const T*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))))
-#define LDL(ptr, c0, stride) (*(const T*)((const char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + s32) * (unsigned)sizeof(T))))
-#define LDLX(ptr, c0, stride, xN) (*(const T*)((const char*)((ptr) + (size_t)(c0) * N) + (size_t)(((unsigned)(stride) * legN + (xN) + s32) * (unsigned)sizeof(T))))
-#define STV(ptr, comp, val) do { if (UNGUARD || live) *(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)
+  WBC_LAUNDERED_TID(tx);
+  WBC_LEG_LANE(SPW, 1, WBC_SRAW_A(SPW))   // (SPW <= 16 states per workgroup: lane_rows.hip.hpp)
+  using RowV = T;
   int jx[3];
   jidx_of_leg(model, a.jpack, leg, jx);
 #ifdef WBC_FUSED_STAMP
@@ -420,10 +409,10 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
     STS(7 + jx[k], qjn[k]);
     if constexpr (!DEFER) {
       if (to_mem) {
-        STV(a.v, 6 + jx[k], vjn[k]);
-        STV(a.q, 7 + jx[k], qjn[k]);
+        if (UNGUARD || live) ROWV(a.v, 6 + jx[k]) = vjn[k];
+        if (UNGUARD || live) ROWV(a.q, 7 + jx[k]) = qjn[k];
       }
-      if (a.tau_traj) STV(a.tau_traj, jx[k], taul[k]);
+      if (a.tau_traj) if (UNGUARD || live) ROWV(a.tau_traj, jx[k]) = taul[k];
     }
   }
   ISTAMP(9);   // joint rows stored
@@ -481,17 +470,17 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       if (to_mem) {
-        STV(a.v, 6 + jx[k], vjn[k]);
-        STV(a.q, 7 + jx[k], qjn[k]);
+        if (UNGUARD || live) ROWV(a.v, 6 + jx[k]) = vjn[k];
+        if (UNGUARD || live) ROWV(a.q, 7 + jx[k]) = qjn[k];
       }
-      if (a.tau_traj) STV(a.tau_traj, jx[k], taul[k]);
+      if (a.tau_traj) if (UNGUARD || live) ROWV(a.tau_traj, jx[k]) = taul[k];
     }
   }
   if (to_mem) {
-    STV(a.v, sel4<int>(leg, 0, 1, 2, 3), sel4<T>(leg, vbn[0], vbn[1], vbn[2], vbn[3]));
-    if (leg < 2) STV(a.v, 4 + leg, leg == 0 ? vbn[4] : vbn[5]);
-    STV(a.q, sel4<int>(leg, 0, 1, 2, 3), sel4<T>(leg, qn[0], qn[1], qn[2], qn[3]));
-    if (leg < 3) STV(a.q, 4 + leg, sel4<T>(leg, qn[4], qn[5], qn[6], qn[6]));
+    if (UNGUARD || live) ROWV(a.v, sel4<int>(leg, 0, 1, 2, 3)) = sel4<T>(leg, vbn[0], vbn[1], vbn[2], vbn[3]);
+    if (leg < 2) if (UNGUARD || live) ROWV(a.v, 4 + leg) = leg == 0 ? vbn[4] : vbn[5];
+    if (UNGUARD || live) ROWV(a.q, sel4<int>(leg, 0, 1, 2, 3)) = sel4<T>(leg, qn[0], qn[1], qn[2], qn[3]);
+    if (leg < 3) if (UNGUARD || live) ROWV(a.q, 4 + leg) = sel4<T>(leg, qn[4], qn[5], qn[6], qn[6]);
   }
   ISTAMP(11);   // base rows stored
   // SCORE: this tick's cost, on the state the tick ends in -- behind the state's stores, where nothing of the integrator is live any more.  A state is spread
@@ -534,11 +523,6 @@ WBC_DEV void integrate_body(const DevModel<T>* __restrict__ model, const Integra
   }
 #undef ISTAMP
 #undef STS
-#undef STV
-#undef LDLX
-#undef LDL
-#undef LDV
-#undef LDU
 }
 
 // PAYLOAD: the plant carries a payload on its trunk (wbc_integrate_plant_batch, and the per-tick launches of the plant rollouts)

@@ -46,30 +46,20 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
   static_assert(!EARLY_BASE || (PART == 0 && EXT != 0), "the early hand-over of rhat_base: whole update, as a role");
   __shared__ T cst_own[EXT ? 1 : CST_WORDS];
   const T* cst = EXT ? cst_ext : cst_own;
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
+  WBC_LAUNDERED_TID(tx);
   const size_t N = a.N;
-  const unsigned N32 = (unsigned)N;
-  const int leg = (int)((tx & 63) >> 4);
-  const size_t s_raw = EXT ? (size_t)blockIdx.x * SPW + (tx & 15) : ((size_t)blockIdx.x * (BLOCK / 64) + (tx >> 6)) * 16 + (tx & 15);
-  const bool slot_ok = SPW == 16 || (int)(tx & 15) < SPW;   // (roles: SPW <= 16 states per workgroup, see WBC_ADDR_MACROS)
-  const bool live = slot_ok && s_raw < N;
-  const unsigned s32 = (unsigned)(live ? s_raw : (slot_ok ? N - 1 : (size_t)blockIdx.x * SPW));
-#define OCS(i) cst[(i) * 4 + leg]
-#define OLDU(ptr, comp) (*(const T*)((const char*)((ptr) + (size_t)(comp) * N) + (size_t)(s32 * (unsigned)sizeof(T))))
-#define OLDV(ptr, comp) (*(const T*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))))
-#define OSTV(ptr, comp, val) do { if (live) *(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)
-#define OST4(ptr, c0, v0_, c1, v1_, c2, v2_, c3, v3_) OSTV(ptr, sel4<int>(leg, c0, c1, c2, c3), sel4<T>(leg, v0_, v1_, v2_, v3_))
+  WBC_LEG_LANE(SPW, 1, EXT ? WBC_SRAW_A(SPW) : WBC_SRAW_W(BLOCK, 1, blockIdx.x))   // (roles: SPW <= 16 states per workgroup, lane_rows.hip.hpp)
+  using RowV = T;
   // rhat: HBM workspace (stand-alone kernel) or the workgroup's LDS image (role)
-#define ORHAT(comp, val) do { if constexpr (EXT != 0) wsl[(comp) * 16 + (int)(tx & 15)] = (val); else OSTV(a.ws, comp, val); } while (0)
+#define ORHAT(comp, val) do { if constexpr (EXT != 0) wsl[(comp) * 16 + (int)(tx & 15)] = (val); else { if (live) ROWV(a.ws, comp) = (val); } } while (0)
   // state loads first, table staging while they are in flight (4-state rollout workgroups: the state is in LDS, see WBC_STATE_MACROS in dyn_split.hip.hpp)
   constexpr bool SIMG = EXT == 3;
   const T* const si_ = SIMG ? a.simg + (int)(s32 - (unsigned)((size_t)blockIdx.x * SPW)) : nullptr;
   T qq[4], vb[6];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) qq[c] = SIMG ? si_[(3 + c) * 16] : OLDU(a.q, 3 + c);
+  for (int c = 0; c < 4; ++c) qq[c] = SIMG ? si_[(3 + c) * 16] : LDU(a.q, 3 + c);
 #pragma unroll
-  for (int c = 0; c < 6; ++c) vb[c] = SIMG ? si_[(SIMG_V + c) * 16] : OLDU(a.v, c);
+  for (int c = 0; c < 6; ++c) vb[c] = SIMG ? si_[(SIMG_V + c) * 16] : LDU(a.v, c);
   int jx[3];
   // (the role keeps the table load: its joint-state loads are not on the tick's critical path -- the QP starts on r_prev -- and with the indices in
   // hand two cycles after entry the fp64 observer-on fused tick, which sits at 255 registers, spills a value)
@@ -78,19 +68,19 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
   T ql[3], vl[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    ql[k] = SIMG ? si_[(7 + jx[k]) * 16] : OLDV(a.q, 7 + jx[k]);
-    vl[k] = SIMG ? si_[(SIMG_V + 6 + jx[k]) * 16] : OLDV(a.v, 6 + jx[k]);
+    ql[k] = SIMG ? si_[(7 + jx[k]) * 16] : LDV(a.q, 7 + jx[k]);
+    vl[k] = SIMG ? si_[(SIMG_V + 6 + jx[k]) * 16] : LDV(a.v, 6 + jx[k]);
   }
   T pre_k1[3] = {0, 0, 0}, pre_k2[3] = {0, 0, 0};
   T pre_fp[3] = {0, 0, 0}, pre_rb[6] = {0, 0, 0, 0, 0, 0}, pre_igb[6] = {0, 0, 0, 0, 0, 0}, pre_rj[3] = {0, 0, 0}, pre_igj[3] = {0, 0, 0}, pre_tp[3] = {0, 0, 0};
   if constexpr (EARLY_BASE) {
     if (prm.observer_order > 0) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) pre_fp[c] = SIMG ? a.resimg[(RES_F + 3 * leg + c) * 16 + (si_ - a.simg)] : OLDV(a.f_prev, 3 * leg + c);
+      for (int c = 0; c < 3; ++c) pre_fp[c] = SIMG ? a.resimg[(RES_F + 3 * leg + c) * 16 + (si_ - a.simg)] : LDV(a.f_prev, 3 * leg + c);
 #pragma unroll
-      for (int c = 0; c < 6; ++c) { pre_rb[c] = OLDU(a.obs_r, c); pre_igb[c] = OLDU(a.obs_integ, c); }
+      for (int c = 0; c < 6; ++c) { pre_rb[c] = LDU(a.obs_r, c); pre_igb[c] = LDU(a.obs_integ, c); }
 #pragma unroll
-      for (int k = 0; k < 3; ++k) { pre_rj[k] = OLDV(a.obs_r, 6 + jx[k]); pre_igj[k] = OLDV(a.obs_integ, 6 + jx[k]); pre_tp[k] = SIMG ? a.resimg[(RES_TAU + jx[k]) * 16 + (si_ - a.simg)] : OLDV(a.tau_prev, jx[k]); }
+      for (int k = 0; k < 3; ++k) { pre_rj[k] = LDV(a.obs_r, 6 + jx[k]); pre_igj[k] = LDV(a.obs_integ, 6 + jx[k]); pre_tp[k] = SIMG ? a.resimg[(RES_TAU + jx[k]) * 16 + (si_ - a.simg)] : LDV(a.tau_prev, jx[k]); }
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {   // gains of my joint rows by a select (no run-time index into the kernel arguments), while those loads are in flight
@@ -144,9 +134,9 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
       T sn, cs;
       sincos_t(ql[k], &sn, &cs);
 #pragma unroll
-      for (int e = 0; e < 9; ++e) E[k].a[e] = OCS(o + e) + cs * OCS(o + 9 + e) + sn * OCS(o + 18 + e);
-      const V3<T> r = mk<T>(OCS(o + 27), OCS(o + 28), OCS(o + 29));
-      const V3<T> ax = mk<T>(OCS(o + 30), OCS(o + 31), OCS(o + 32));
+      for (int e = 0; e < 9; ++e) E[k].a[e] = CS(o + e) + cs * CS(o + 9 + e) + sn * CS(o + 18 + e);
+      const V3<T> r = mk<T>(CS(o + 27), CS(o + 28), CS(o + 29));
+      const V3<T> ax = mk<T>(CS(o + 30), CS(o + 31), CS(o + 32));
       om[k] = tmul(E[k], omp) + ax * vl[k];
       vv[k] = tmul(E[k], vp + cross(omp, r));
       gL[k] = tmul(E[k], gp);
@@ -155,18 +145,18 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
   }
   // ---- return sweep: subtree momentum / weight, their projections on the joint axes, foot geometry
   T p_leg[3], beta_l[3];
-  V3<T> dft = mk<T>(OCS(129), OCS(130), OCS(131));
+  V3<T> dft = mk<T>(CS(129), CS(130), CS(131));
   V3<T> jc[3];
   SF<T> macc, gacc;
 #pragma unroll
   for (int k = 2; k >= 0; --k) {
     const int o = JOINT_WORDS * k;
-    const V3<T> r = mk<T>(OCS(o + 27), OCS(o + 28), OCS(o + 29));
-    const V3<T> ax = mk<T>(OCS(o + 30), OCS(o + 31), OCS(o + 32));
-    const T m = OCS(o + 33);
-    const V3<T> h = mk<T>(OCS(o + 34), OCS(o + 35), OCS(o + 36));
+    const V3<T> r = mk<T>(CS(o + 27), CS(o + 28), CS(o + 29));
+    const V3<T> ax = mk<T>(CS(o + 30), CS(o + 31), CS(o + 32));
+    const T m = CS(o + 33);
+    const V3<T> h = mk<T>(CS(o + 34), CS(o + 35), CS(o + 36));
     S3<T> Io;
-    Io.xx = OCS(o + 37); Io.xy = OCS(o + 38); Io.xz = OCS(o + 39); Io.yy = OCS(o + 40); Io.yz = OCS(o + 41); Io.zz = OCS(o + 42);
+    Io.xx = CS(o + 37); Io.xy = CS(o + 38); Io.xz = CS(o + 39); Io.yy = CS(o + 40); Io.yz = CS(o + 41); Io.zz = CS(o + 42);
     SF<T> mk_ = inertia_mul(m, h, Io, om[k], vv[k]), gk;
     gk.n = cross(h, gL[k]);
     gk.f = gL[k] * m;
@@ -235,12 +225,12 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
       }
       after_base(1);
       before_store();
-      OST4(a.obs_integ, 0, p_b[0], 1, p_b[1], 2, p_b[2], 3, p_b[3]);
-      if (leg < 2) OSTV(a.obs_integ, 4 + leg, leg == 0 ? p_b[4] : p_b[5]);
-      OST4(a.obs_r, 0, rb[0], 1, rb[1], 2, rb[2], 3, rb[3]);
-      if (leg < 2) OSTV(a.obs_r, 4 + leg, leg == 0 ? rb[4] : rb[5]);
+      if (live) ROWV4(a.obs_integ, leg, 0, 1, 2, 3) = sel4<T>(leg, p_b[0], p_b[1], p_b[2], p_b[3]);
+      if (leg < 2) if (live) ROWV(a.obs_integ, 4 + leg) = leg == 0 ? p_b[4] : p_b[5];
+      if (live) ROWV4(a.obs_r, leg, 0, 1, 2, 3) = sel4<T>(leg, rb[0], rb[1], rb[2], rb[3]);
+      if (leg < 2) if (live) ROWV(a.obs_r, 4 + leg) = leg == 0 ? rb[4] : rb[5];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) { OSTV(a.obs_integ, 6 + jx[k], igj[k]); OSTV(a.obs_r, 6 + jx[k], rl[k]); }
+      for (int k = 0; k < 3; ++k) { if (live) ROWV(a.obs_integ, 6 + jx[k]) = igj[k]; if (live) ROWV(a.obs_r, 6 + jx[k]) = rl[k]; }
     } else {   // (observer off in an observer kernel: not launched that way, but the QP must not wait for ever)
       ORHAT(sel4<int>(leg, WS_RHAT + 0, WS_RHAT + 1, WS_RHAT + 2, WS_RHAT + 3), (T)0);
       if (leg < 2) ORHAT(WS_RHAT + 4 + leg, (T)0);
@@ -254,7 +244,7 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
     // (SIMG: tau_prev, f_prev are the rows the previous tick's QP left in the workgroup's result image -- nothing of them is in memory before the last tick)
     const T* const rimg = SIMG ? a.resimg + (si_ - a.simg) : nullptr;
     const V3<T> fp = SIMG ? mk<T>(rimg[(RES_F + 3 * leg + 0) * 16], rimg[(RES_F + 3 * leg + 1) * 16], rimg[(RES_F + 3 * leg + 2) * 16])
-                          : mk<T>(OLDV(a.f_prev, 3 * leg + 0), OLDV(a.f_prev, 3 * leg + 1), OLDV(a.f_prev, 3 * leg + 2));
+                          : mk<T>(LDV(a.f_prev, 3 * leg + 0), LDV(a.f_prev, 3 * leg + 1), LDV(a.f_prev, 3 * leg + 2));
     const T dt = prm.dt;
     const bool o1 = prm.observer_order == 1;
     if constexpr (BASE) {
@@ -263,8 +253,8 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
       xrow_sum_k<T, 6>(ub);
 #pragma unroll
       for (int c = 0; c < 6; ++c) {
-        const T r0 = OLDU(a.obs_r, c);
-        const T ig = OLDU(a.obs_integ, c) + dt * (ub[c] + beta_b[c] + r0);
+        const T r0 = LDU(a.obs_r, c);
+        const T ig = LDU(a.obs_integ, c) + dt * (ub[c] + beta_b[c] + r0);
         const T e = p_b[c] - ig;
         rb[c] = o1 ? prm.K1[c] * e : r0 + dt * prm.K2[c] * (prm.K1[c] * e - r0);
         p_b[c] = ig;
@@ -272,24 +262,24 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
       // every lane's loads of the replicated rows feed its own store values: all loads of a row have returned in every lane
       // of the wave before any lane stores to it
       before_store();
-      OST4(a.obs_integ, 0, p_b[0], 1, p_b[1], 2, p_b[2], 3, p_b[3]);
-      if (leg < 2) OSTV(a.obs_integ, 4 + leg, leg == 0 ? p_b[4] : p_b[5]);
-      OST4(a.obs_r, 0, rb[0], 1, rb[1], 2, rb[2], 3, rb[3]);
-      if (leg < 2) OSTV(a.obs_r, 4 + leg, leg == 0 ? rb[4] : rb[5]);
+      if (live) ROWV4(a.obs_integ, leg, 0, 1, 2, 3) = sel4<T>(leg, p_b[0], p_b[1], p_b[2], p_b[3]);
+      if (leg < 2) if (live) ROWV(a.obs_integ, 4 + leg) = leg == 0 ? p_b[4] : p_b[5];
+      if (live) ROWV4(a.obs_r, leg, 0, 1, 2, 3) = sel4<T>(leg, rb[0], rb[1], rb[2], rb[3]);
+      if (leg < 2) if (live) ROWV(a.obs_r, 4 + leg) = leg == 0 ? rb[4] : rb[5];
     }
 #pragma unroll
     for (int k = 0; k < (JOINTS ? 3 : 0); ++k) {
       const int c = 6 + jx[k];
-      const T r0 = OLDV(a.obs_r, c);
-      const T u = (SIMG ? rimg[(RES_TAU + jx[k]) * 16] : OLDV(a.tau_prev, jx[k])) + dot(jw[k], fp);
-      const T ig = OLDV(a.obs_integ, c) + dt * (u + beta_l[k] + r0);
+      const T r0 = LDV(a.obs_r, c);
+      const T u = (SIMG ? rimg[(RES_TAU + jx[k]) * 16] : LDV(a.tau_prev, jx[k])) + dot(jw[k], fp);
+      const T ig = LDV(a.obs_integ, c) + dt * (u + beta_l[k] + r0);
       const T e = p_leg[k] - ig;
       T k1 = prm.K1[6], k2 = prm.K2[6];   // gains of joint row c by a select (no run-time index into the kernel arguments)
 #pragma unroll
       for (int j = 1; j < 12; ++j) { k1 = (jx[k] == j) ? prm.K1[6 + j] : k1; k2 = (jx[k] == j) ? prm.K2[6 + j] : k2; }
       rl[k] = o1 ? k1 * e : r0 + dt * k2 * (k1 * e - r0);
-      OSTV(a.obs_integ, c, ig);
-      OSTV(a.obs_r, c, rl[k]);
+      if (live) ROWV(a.obs_integ, c) = ig;
+      if (live) ROWV(a.obs_r, c) = rl[k];
     }
   }
   if constexpr (BASE) {
@@ -302,11 +292,6 @@ WBC_DEV void observer_body(const DevModel<T>* __restrict__ model, const DevParam
   }
   }
 #undef ORHAT
-#undef OST4
-#undef OSTV
-#undef OLDV
-#undef OLDU
-#undef OCS
 }
 
 // ======================================================================================================================
@@ -330,31 +315,23 @@ WBC_DEV void observer_park_body(const DevModel<T>* __restrict__ model, const Dev
   T (&kgain)[36] = lds.kgain;
   V (&park)[3 * PKW][BLOCK] = lds.park;
   unsigned tx = threadIdx.x & (unsigned)(BLOCK - 1);   // (thread within the BLOCK threads that run this body)
-  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
+  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (lane_rows.hip.hpp)
   const size_t N = a.N;
-  const unsigned N32 = (unsigned)N;
-  const int leg = (int)((tx & 63) >> 4);
-  const size_t s_raw = (((size_t)blk * (BLOCK / 64) + (tx >> 6)) * 16 + (tx & 15)) * W;   // first state of this lane (W = 2: N is even)
-  const bool live = s_raw < N;
-  const unsigned s32 = (unsigned)(live ? s_raw : N - W);
-#define OCS(i) cst[(i) * 4 + leg]
-#define OLDU(ptr, comp) (*(const V*)((const char*)((ptr) + (size_t)(comp) * N) + (size_t)(s32 * (unsigned)sizeof(T))))
-#define OLDV(ptr, comp) (*(const V*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))))
-#define OSTV(ptr, comp, val) do { if (live) *(V*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val); } while (0)
-#define OST4(ptr, c0, v0_, c1, v1_, c2, v2_, c3, v3_) OSTV(ptr, sel4<int>(leg, c0, c1, c2, c3), sel4<V>(leg, v0_, v1_, v2_, v3_))
+  WBC_LEG_LANE(16, W, WBC_SRAW_W(BLOCK, W, blk))
+  using RowV = V;
   // state loads first, table staging while they are in flight
   V qq[4], vb[6];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) qq[c] = OLDU(a.q, 3 + c);
+  for (int c = 0; c < 4; ++c) qq[c] = LDU(a.q, 3 + c);
 #pragma unroll
-  for (int c = 0; c < 6; ++c) vb[c] = OLDU(a.v, c);
+  for (int c = 0; c < 6; ++c) vb[c] = LDU(a.v, c);
   int jx[3];
   jidx_of_leg(model, a.jpack, leg, jx);
   V ql[3], vl[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    ql[k] = OLDV(a.q, 7 + jx[k]);
-    vl[k] = OLDV(a.v, 6 + jx[k]);
+    ql[k] = LDV(a.q, 7 + jx[k]);
+    vl[k] = LDV(a.v, 6 + jx[k]);
   }
   // branch-free staging (clamped index, the tail lanes rewrite the last word): with a divergent staging loop here hipcc 7.2 put
   // VGPR spill stores of the fp64 build into the loop's exit block BEFORE exec is restored, i.e. with no lane enabled
@@ -380,7 +357,7 @@ WBC_DEV void observer_park_body(const DevModel<T>* __restrict__ model, const Dev
   __syncthreads();
   const int hcol = xr.col0 + (int)(tx & 15) * W;   // (XR) my first state's column of the tile
   (void)hcol;
-#define ORH(comp, val) do { if constexpr (XR) *(V*)(xr.hand + ((comp) - WS_RHAT + HAND_RHAT) * xr.hs + hcol) = (val); else OSTV(a.ws, comp, val); } while (0)   /* rhat for the QP stage */
+#define ORH(comp, val) do { if constexpr (XR) *(V*)(xr.hand + ((comp) - WS_RHAT + HAND_RHAT) * xr.hs + hcol) = (val); else { if (live) ROWV(a.ws, comp) = (val); } } while (0)   /* rhat for the QP stage */
 
   V qx, qy, qz, qw;
   {
@@ -415,7 +392,7 @@ WBC_DEV void observer_park_body(const DevModel<T>* __restrict__ model, const Dev
   auto joint_E = [&](int k, V sn, V cs, M3<V>& Ek) __attribute__((always_inline)) {
     const int o = JOINT_WORDS * k;
 #pragma unroll
-    for (int e = 0; e < 9; ++e) Ek.a[e] = OCS(o + e) + cs * OCS(o + 9 + e) + sn * OCS(o + 18 + e);
+    for (int e = 0; e < 9; ++e) Ek.a[e] = CS(o + e) + cs * CS(o + 9 + e) + sn * CS(o + 18 + e);
   };
   {
     V3<V> omp = om0, vp = v0, gp = gneg;
@@ -426,8 +403,8 @@ WBC_DEV void observer_park_body(const DevModel<T>* __restrict__ model, const Dev
       sincos_t(ql[k], &sn, &cs);
       M3<V> Ek;
       joint_E(k, sn, cs, Ek);
-      const V3<V> r = mk<V>(OCS(o + 27), OCS(o + 28), OCS(o + 29));
-      const V3<V> ax = mk<V>(OCS(o + 30), OCS(o + 31), OCS(o + 32));
+      const V3<V> r = mk<V>(CS(o + 27), CS(o + 28), CS(o + 29));
+      const V3<V> ax = mk<V>(CS(o + 30), CS(o + 31), CS(o + 32));
       const V3<V> omk = tmul(Ek, omp) + ax * vl[k];
       const V3<V> vvk = tmul(Ek, vp + cross(omp, r));
       const V3<V> gk = tmul(Ek, gp);
@@ -450,28 +427,28 @@ WBC_DEV void observer_park_body(const DevModel<T>* __restrict__ model, const Dev
   V3<V> fp = mk<V>(0, 0, 0);
   V in_r[3] = {0, 0, 0}, in_ig[3] = {0, 0, 0}, in_tp[3] = {0, 0, 0}, in_rb[6] = {0, 0, 0, 0, 0, 0}, in_igb[6] = {0, 0, 0, 0, 0, 0};
   if (obs_on) {
-    fp = mk<V>(OLDV(a.f_prev, 3 * leg + 0), OLDV(a.f_prev, 3 * leg + 1), OLDV(a.f_prev, 3 * leg + 2));
+    fp = mk<V>(LDV(a.f_prev, 3 * leg + 0), LDV(a.f_prev, 3 * leg + 1), LDV(a.f_prev, 3 * leg + 2));
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { in_r[k] = OLDV(a.obs_r, 6 + jx[k]); in_ig[k] = OLDV(a.obs_integ, 6 + jx[k]); in_tp[k] = OLDV(a.tau_prev, jx[k]); }
+    for (int k = 0; k < 3; ++k) { in_r[k] = LDV(a.obs_r, 6 + jx[k]); in_ig[k] = LDV(a.obs_integ, 6 + jx[k]); in_tp[k] = LDV(a.tau_prev, jx[k]); }
 #pragma unroll
-    for (int c = 0; c < 6; ++c) { in_rb[c] = OLDU(a.obs_r, c); in_igb[c] = OLDU(a.obs_integ, c); }
+    for (int c = 0; c < 6; ++c) { in_rb[c] = LDU(a.obs_r, c); in_igb[c] = LDU(a.obs_integ, c); }
   }
 #pragma unroll
-  for (int c = 0; c < 6; ++c) vb[c] = OLDU(a.v, c);   // the base velocity again, for base_state after the sweep
+  for (int c = 0; c < 6; ++c) vb[c] = LDU(a.v, c);   // the base velocity again, for base_state after the sweep
   // ---- return sweep: subtree momentum / weight, their projections on the joint axes, foot geometry
   V p_leg[3], beta_l[3];
-  V3<V> dft = mk<V>(OCS(129), OCS(130), OCS(131));
+  V3<V> dft = mk<V>(CS(129), CS(130), CS(131));
   V3<V> jc[3];
   SF<V> macc, gacc;
 #pragma unroll
   for (int k = 2; k >= 0; --k) {
     const int o = JOINT_WORDS * k;
-    const V3<V> r = mk<V>(OCS(o + 27), OCS(o + 28), OCS(o + 29));
-    const V3<V> ax = mk<V>(OCS(o + 30), OCS(o + 31), OCS(o + 32));
-    const V m = OCS(o + 33);
-    const V3<V> h = mk<V>(OCS(o + 34), OCS(o + 35), OCS(o + 36));
+    const V3<V> r = mk<V>(CS(o + 27), CS(o + 28), CS(o + 29));
+    const V3<V> ax = mk<V>(CS(o + 30), CS(o + 31), CS(o + 32));
+    const V m = CS(o + 33);
+    const V3<V> h = mk<V>(CS(o + 34), CS(o + 35), CS(o + 36));
     S3<V> Io;
-    Io.xx = OCS(o + 37); Io.xy = OCS(o + 38); Io.xz = OCS(o + 39); Io.yy = OCS(o + 40); Io.yz = OCS(o + 41); Io.zz = OCS(o + 42);
+    Io.xx = CS(o + 37); Io.xy = CS(o + 38); Io.xz = CS(o + 39); Io.yy = CS(o + 40); Io.yz = CS(o + 41); Io.zz = CS(o + 42);
     const V* pk = &park[PKW * k][tx];
     M3<V> Ek;
     joint_E(k, pk[0], pk[BLOCK], Ek);
@@ -528,8 +505,8 @@ WBC_DEV void observer_park_body(const DevModel<T>* __restrict__ model, const Dev
         const V e = p_leg[k] - ig;
         const T k1 = kgain[c], k2 = kgain[18 + c];
         rl[k] = o1 ? k1 * e : r0 + dt * k2 * (k1 * e - r0);
-        OSTV(a.obs_integ, c, ig);
-        OSTV(a.obs_r, c, rl[k]);
+        if (live) ROWV(a.obs_integ, c) = ig;
+        if (live) ROWV(a.obs_r, c) = rl[k];
       }
     }
 #pragma unroll
@@ -567,20 +544,15 @@ WBC_DEV void observer_park_body(const DevModel<T>* __restrict__ model, const Dev
         p_b[c] = ig;
       }
       // (the replicated rows were read by every lane of the wave long before any lane stores to them)
-      OST4(a.obs_integ, 0, p_b[0], 1, p_b[1], 2, p_b[2], 3, p_b[3]);
-      if (leg < 2) OSTV(a.obs_integ, 4 + leg, leg == 0 ? p_b[4] : p_b[5]);
-      OST4(a.obs_r, 0, rb[0], 1, rb[1], 2, rb[2], 3, rb[3]);
-      if (leg < 2) OSTV(a.obs_r, 4 + leg, leg == 0 ? rb[4] : rb[5]);
+      if (live) ROWV4(a.obs_integ, leg, 0, 1, 2, 3) = sel4<V>(leg, p_b[0], p_b[1], p_b[2], p_b[3]);
+      if (leg < 2) if (live) ROWV(a.obs_integ, 4 + leg) = leg == 0 ? p_b[4] : p_b[5];
+      if (live) ROWV4(a.obs_r, leg, 0, 1, 2, 3) = sel4<V>(leg, rb[0], rb[1], rb[2], rb[3]);
+      if (leg < 2) if (live) ROWV(a.obs_r, 4 + leg) = leg == 0 ? rb[4] : rb[5];
     }
     ORH(sel4<int>(leg, WS_RHAT + 0, WS_RHAT + 1, WS_RHAT + 2, WS_RHAT + 3), sel4<V>(leg, rb[0], rb[1], rb[2], rb[3]));
     if (leg < 2) ORH(WS_RHAT + 4 + leg, leg == 0 ? rb[4] : rb[5]);
   }
 #undef ORH
-#undef OST4
-#undef OSTV
-#undef OLDV
-#undef OLDU
-#undef OCS
 }
 
 constexpr int WBC_OBS_WAVES = 2;

@@ -208,7 +208,7 @@ WBC_DEV void qp_group16_body(const DevParams<T>& prm, const QpArgs<T>& a, const 
   // WPB: wavefronts of the workgroup that run this body (the fused kernels pair their producer wavefronts with four QP wavefronts)
   __shared__ G16Lds<T> lds_all[WPB];
   unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // lane-derived predicates stay inside this call (see WBC_LAUNDERED_TID, dyn_split.hip.hpp)
+  asm volatile("" : "+v"(tx));   // lane-derived predicates stay inside this call (see WBC_LAUNDERED_TID, lane_rows.hip.hpp)
   const int lane = tx & 63;
   const int l16 = lane & 15;
   const int rowbase = lane & 48;   // first lane of my 16-lane row

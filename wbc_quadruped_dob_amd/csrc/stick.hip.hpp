@@ -3,7 +3,7 @@
 // 3k .. 3k+2 = the world point foot k is stuck to) and stick [N] (in: bit k = foot k has an anchor; out: bit k = loaded, bit 4+k = slid this tick).
 // p_f, v_f, phi, v_n, v_t, f_n, the contact bit and the gap are formed exactly as ground_law forms them.  The lines are restated here and not shared:
 // behind a common helper (two shapes tried, docs/DESIGN_HISTORY.md) k_ground assembles as before and this unit keeps its instruction counts, but its
-// loads are scheduled differently and stick_force_kernel measured 5 - 10 % slower.  Only the addresses (FootAddr) and the lane mapping (foot_lane) are
+// loads are scheduled differently and stick_force_kernel measured 5 - 10 % slower.  Only the addresses (LaneRows) and the lane mapping (foot_lane, LegLane) are
 // ground.hip.hpp's.  Then, per foot:
 //   f_n == 0:  f_t = 0, both out bits clear, the anchor words untouched
 //   f_n  > 0:  a = in bit ? anchor : p_f          (first loaded tick: the anchor is dropped where the foot is)
@@ -42,23 +42,23 @@ template <class T> struct StickOut {
 template <class T>
 WBC_DEV V3<T> stick_law(const T* __restrict__ q, const T* __restrict__ v, const T* __restrict__ Jc, const GroundIO<T>& g, const StickIO<T>& sk,
                         unsigned long long jpack, int leg, unsigned s32, unsigned N32, StickOut<T>& o) {
-  const FootAddr A(leg, s32, N32);
+  const LaneRows A(leg, s32, N32);
   int jx[3];
   jidx_of_leg((const DevModel<T>*)nullptr, jpack, leg, jx);
   // (ground_law's loads and arithmetic, word for word, down to f_n: a change there is a change here, contraction included)
-  const V3<T> dl = mk<T>(Jc[A.leg_row(18 * 1 + 5, 54)], Jc[A.leg_row(18 * 2 + 3, 54)], Jc[A.leg_row(18 * 0 + 4, 54)]);
+  const V3<T> dl = mk<T>(Jc[A.leg_idx(18 * 1 + 5, 54)], Jc[A.leg_idx(18 * 2 + 3, 54)], Jc[A.leg_idx(18 * 0 + 4, 54)]);
   T jcl[3][3], qd[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int col = 6 + jx[k];
-    jcl[0][k] = Jc[A.leg_row(0 + col, 54)]; jcl[1][k] = Jc[A.leg_row(18 + col, 54)]; jcl[2][k] = Jc[A.leg_row(36 + col, 54)];
-    qd[k] = v[A.row(col)];
+    jcl[0][k] = Jc[A.leg_idx(0 + col, 54)]; jcl[1][k] = Jc[A.leg_idx(18 + col, 54)]; jcl[2][k] = Jc[A.leg_idx(36 + col, 54)];
+    qd[k] = v[A.idx(col)];
   }
-  const V3<T> pb = mk<T>(q[A.row(0)], q[A.row(1)], q[A.row(2)]);
-  const V3<T> vb = mk<T>(v[A.row(0)], v[A.row(1)], v[A.row(2)]), om = mk<T>(v[A.row(3)], v[A.row(4)], v[A.row(5)]);
-  const V3<T> n = mk<T>(g.normals[A.leg_row(0, 3)], g.normals[A.leg_row(1, 3)], g.normals[A.leg_row(2, 3)]);
-  const T d = g.height[A.leg_row(0, 1)], mu = g.mu[A.leg_row(0, 1)];
-  const V3<T> a_in = mk<T>(sk.anchor[A.leg_row(0, 3)], sk.anchor[A.leg_row(1, 3)], sk.anchor[A.leg_row(2, 3)]);
+  const V3<T> pb = mk<T>(q[A.idx(0)], q[A.idx(1)], q[A.idx(2)]);
+  const V3<T> vb = mk<T>(v[A.idx(0)], v[A.idx(1)], v[A.idx(2)]), om = mk<T>(v[A.idx(3)], v[A.idx(4)], v[A.idx(5)]);
+  const V3<T> n = mk<T>(g.normals[A.leg_idx(0, 3)], g.normals[A.leg_idx(1, 3)], g.normals[A.leg_idx(2, 3)]);
+  const T d = g.height[A.leg_idx(0, 1)], mu = g.mu[A.leg_idx(0, 1)];
+  const V3<T> a_in = mk<T>(sk.anchor[A.leg_idx(0, 3)], sk.anchor[A.leg_idx(1, 3)], sk.anchor[A.leg_idx(2, 3)]);
   const bool had = ((sk.stick[s32] >> leg) & 1) != 0;
   const V3<T> pf = pb + dl;
   const V3<T> vf = vb + cross(om, dl) + mk<T>(jcl[0][0] * qd[0] + jcl[0][1] * qd[1] + jcl[0][2] * qd[2],
@@ -116,7 +116,7 @@ WBC_DEV void stick_store(const GroundIO<T>& g, const StickIO<T>& sk, int leg, un
 
 template <class T>
 __global__ __launch_bounds__(64) void stick_force_kernel(StickArgs<T> a) {
-  const FootLane l = foot_lane(a.N);
+  const LegLane l = foot_lane(a.N);
   StickOut<T> o;
   const V3<T> f = stick_law<T>(a.q, a.v, a.Jc, a.g, a.s, a.jpack, l.leg, l.s32, (unsigned)a.N, o);
   stick_store<T>(a.g, a.s, l.leg, l.st, l.s32, (unsigned)a.N, l.live, f, o);
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64) void stick_force_kernel(StickArgs<T> a) {
 
 template <class T>
 __global__ __launch_bounds__(64) void stick_integrate_kernel(const DevModel<T>* __restrict__ model, StickIntegrateArgs<T> a) {
-  const FootLane l = foot_lane(a.N);
+  const LegLane l = foot_lane(a.N);
   StickOut<T> o;
   const V3<T> f = stick_law<T>(a.q, a.v, a.Jc, a.g, a.s, a.jpack, l.leg, l.s32, (unsigned)a.N, o);
   stick_store<T>(a.g, a.s, l.leg, l.st, l.s32, (unsigned)a.N, l.live, f, o);

@@ -24,7 +24,6 @@ namespace wbc {
 template <class T>
 WBC_DEV void swing_leg_cmd(const T* cst, int leg, const M3<T>& R, V3<T> pb, V3<T> vlin, V3<T> om0, const M3<T> (&E)[3], const T (&vl)[3],
                            const T (&bacc)[6], const T (&sw)[9], T t, const DevSwingParams<T>& P, T (&qdd)[3], V3<T>& pf, V3<T>& jv) {
-#define RCS(i) cst[(i) * 4 + leg]
   M3<T> A = E[0];                       // link k -> base
   V3<T> o = mk<T>((T)0, (T)0, (T)0);    // origin of link k, base coordinates
   V3<T> z[3], oj[3];
@@ -32,8 +31,8 @@ WBC_DEV void swing_leg_cmd(const T* cst, int leg, const M3<T>& R, V3<T> pb, V3<T
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int ok = JOINT_WORDS * k;
-    const V3<T> r = mk<T>(RCS(ok + 27), RCS(ok + 28), RCS(ok + 29));
-    const V3<T> ax = mk<T>(RCS(ok + 30), RCS(ok + 31), RCS(ok + 32));
+    const V3<T> r = mk<T>(CS(ok + 27), CS(ok + 28), CS(ok + 29));
+    const V3<T> ax = mk<T>(CS(ok + 30), CS(ok + 31), CS(ok + 32));
     const V3<T> l = k == 0 ? r : mul(A, r);   // o_k - o_(k-1)
     ao = ao + cross(al, l) + cross(Om, cross(Om, l));
     vo = vo + cross(Om, l);
@@ -51,7 +50,7 @@ WBC_DEV void swing_leg_cmd(const T* cst, int leg, const M3<T>& R, V3<T> pb, V3<T
     Om = Om + zk * vl[k];
     z[k] = zk; oj[k] = o;
   }
-  const V3<T> lf = mul(A, mk<T>(RCS(3 * JOINT_WORDS), RCS(3 * JOINT_WORDS + 1), RCS(3 * JOINT_WORDS + 2)));
+  const V3<T> lf = mul(A, mk<T>(CS(3 * JOINT_WORDS), CS(3 * JOINT_WORDS + 1), CS(3 * JOINT_WORDS + 2)));
   const V3<T> d = o + lf;                                                   // foot relative to the base origin
   const V3<T> af = ao + cross(al, lf) + cross(Om, cross(Om, lf));           // Jdot_k v, base coordinates
   const V3<T> vf = vo + cross(Om, lf);
@@ -106,7 +105,6 @@ WBC_DEV void swing_leg_cmd(const T* cst, int leg, const M3<T>& R, V3<T> pb, V3<T
                         (c02 * rhs.x + c12 * rhs.y + c22 * rhs.z) * idet);
 #pragma unroll
   for (int k = 0; k < 3; ++k) qdd[k] = dot(C[k], y);
-#undef RCS
 }
 
 // the plan words and mask bit of the lane's leg, the command, the foot rows (by their owner lane); swing legs' qdd replace adj
@@ -151,24 +149,19 @@ __global__ __launch_bounds__(64) void swing_reference_kernel(const DevModel<T>* 
   __shared__ T cst[CST_WORDS];
   for (int i = threadIdx.x; i < CST_WORDS; i += blockDim.x) cst[i] = model->cst[i];
   __syncthreads();
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // see WBC_LAUNDERED_TID (dyn_split.hip.hpp)
+  WBC_LAUNDERED_TID(tx);
   const size_t N = a.N;
-  const int leg = (int)((tx & 63) >> 4);
-  const size_t s_raw = (size_t)blockIdx.x * 16 + (tx & 15);
-  const bool live = s_raw < N;
-  const unsigned s32 = (unsigned)(live ? s_raw : N - 1);   // lanes beyond the batch recompute its last state and store nothing
-#define RLD(ptr, comp) ((ptr)[(size_t)(comp) * N + s32])
+  WBC_LEG_LANE(16, 1, WBC_SRAW_A(16))   // lanes beyond the batch recompute its last state and store nothing.  (The macro form: through leg_lane() this kernel's device code moved)
   T qb[7], vb[6], bacc[6];
 #pragma unroll
-  for (int c = 0; c < 7; ++c) qb[c] = RLD(a.q, c);
+  for (int c = 0; c < 7; ++c) qb[c] = ROWI(a.q, c);
 #pragma unroll
-  for (int c = 0; c < 6; ++c) { vb[c] = RLD(a.v, c); bacc[c] = RLD(a.vdot_des, c); }
+  for (int c = 0; c < 6; ++c) { vb[c] = ROWI(a.v, c); bacc[c] = ROWI(a.vdot_des, c); }
   int jx[3];
   jidx_of_leg(model, a.jpack, leg, jx);
   T ql[3], vl[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { ql[k] = RLD(a.q, 7 + jx[k]); vl[k] = RLD(a.v, 6 + jx[k]); }
+  for (int k = 0; k < 3; ++k) { ql[k] = ROWI(a.q, 7 + jx[k]); vl[k] = ROWI(a.v, 6 + jx[k]); }
   M3<T> R;
   {
     const T n = rsqrt_t(qb[3] * qb[3] + qb[4] * qb[4] + qb[5] * qb[5] + qb[6] * qb[6]);
@@ -185,15 +178,14 @@ __global__ __launch_bounds__(64) void swing_reference_kernel(const DevModel<T>* 
     T sn, cs;
     sincos_t(ql[k], &sn, &cs);
 #pragma unroll
-    for (int e = 0; e < 9; ++e) E[k].a[e] = cst[(o + e) * 4 + leg] + cs * cst[(o + 9 + e) * 4 + leg] + sn * cst[(o + 18 + e) * 4 + leg];
+    for (int e = 0; e < 9; ++e) E[k].a[e] = CS(o + e) + cs * CS(o + 9 + e) + sn * CS(o + 18 + e);
   }
   T adj[3] = {(T)0, (T)0, (T)0};
   swing_apply<T>(a.s, cst, leg, N, s32, live, R, qb, vb, om0, E, vl, bacc, a.t, adj);
   if (live && ((a.s.mask[s32] >> leg) & 1) == 0) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) RLD(a.vdot_des, 6 + jx[k]) = adj[k];
+    for (int k = 0; k < 3; ++k) ROWI(a.vdot_des, 6 + jx[k]) = adj[k];
   }
-#undef RLD
 }
 
 }  // namespace wbc
