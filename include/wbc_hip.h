@@ -644,6 +644,71 @@ int wbc_integrate_ground_stick_batch(wbc_solver* s, size_t N, void* q, void* v, 
                                      const void* normals, const void* height, const void* mu, const void* tau_ext /* may be NULL */, void* anchor,
                                      int* stick, void* f_gr, int* contact /* may be NULL */, void* gap /* may be NULL */, void* stream);
 
+/* Contact sensing from the disturbance observer: estimated foot forces and a contact word with hysteresis.  ADDITIVE to ABI 10 (wbc_abi_version()
+ * stays 10, no existing struct, call or default changes; detect it by these symbols).  The `contact` word the ground calls produce is the plant's own
+ * normal force: simulator ground truth.  A controller on a robot has the momentum observer's residual r instead.  The observer's update is
+ *   integ += dt (S^T tau_prev + Jc^T f_prev + beta + r),   r = K1 (M v - integ),
+ * so r estimates the generalized force that acts beyond the planned Jc^T f_prev: on the ground, Jc^T (f_gr - f_prev), low-passed with the time
+ * constant 1 / K1.  The joint rows of a leg see only that leg's own foot, so the estimate needs no base rows and no 12 x 12 solve.  Inputs, device
+ * pointers, component-major, solver scalar type:
+ *   Jc      [3 nf nv][N]  the last wbc_step_batch's out->Jc
+ *   r       [nv][N]       the observer residual AFTER that step (wbc_obs_state.r)
+ *   f_prev  [12][N]       the buffer that step was given as in->f_prev
+ *   normals [12][N]       the tick's contact normals
+ *   contact [N] int       IN/OUT.  in: bits 0-3 = the previous estimate (the caller stores 0 before the first call).  Only bits 0-3 are read or
+ *                         written; the other bits are kept.
+ * Per foot k, with J_leg,k the own-leg 3x3 block of Jc (the words wbc_integrate_batch and the ground calls read; the leg's joint columns come from
+ * the model, so joint orders that are not leg-major work) and r_joint its three joint rows of r:
+ *   A      = J_leg,k^T
+ *   det    = det A
+ *   ok     = |det| > det_min
+ *   df     = ok ? adj(A) r_joint / det : 0      (the adjugate form: no pivoting, and no division when !ok)
+ *   f_est  = f_prev,k + df
+ *   fn     = n_k . f_est
+ *   bit k  = !ok ? the previous bit : (the previous bit ? fn > f_off : fn > f_on)
+ * Outputs: contact [N] (bits 0-3); f_est [12][N] or NULL; fn_est [4][N] or NULL; singular [N] int or NULL (bit k = !ok).
+ * wbc_contact_estimate_batch evaluates the law alone.  wbc_gait_estimated_batch evaluates it and then runs wbc_gait_batch's rule on the word it has
+ * just formed, in ONE launch; every output is bit for bit what wbc_contact_estimate_batch followed by wbc_gait_batch(contact = that word) gives.
+ * The walking tick stays at four launches:
+ *   gait_estimated -> reference_swing -> step (observer on) -> integrate_ground[_stick]
+ * Both calls work under either observer_order.  With observer_order = 0 the step does not write r: the caller simply has no meaningful residual (a
+ * zero r gives f_est = f_prev).  The estimate lags the true force by about 1 / K1 (20 ms = 20 ticks of 2^-10 s with the default K1 = 50); an early
+ * touchdown on a 15 mm bump came 3 ticks after the plant's own bit, since the force there rises far past f_on and only the start of the lag shows.
+ * The defaults
+ *   f_on = 15 N,  f_off = 5 N,  det_min = 1.5e-3 m^3
+ * were fixed on the CPU with the numpy restatement of this law (tests/contact_ref.py) in the walking loop of the ground plant with the observer on
+ * (observer_order = 1, K1 = 50, dt = 2^-10, a 15 mm bump under one foot).  Tried, f_on / f_off: 5 / 5 (the plant's f_touch, no hysteresis) finds every
+ * early touchdown the plant's own bits give, but one bit chattered 0 -> 1 -> 0 on consecutive ticks in the 16-robot loop: it did NOT pass.  10 / 5
+ * does not chatter, but its smallest threshold margin is 1.9e-6 of the largest force, next to the 1e-6 the tests ask for.  15 / 5 does not chatter, finds
+ * every bumped foot 3 ticks behind the plant's bit and keeps a margin of 2.2e-5.  30 / 5 finds 4 of 18 early touchdowns and the bumped feet 7 and 8 ticks late.
+ * Every one of these loops stayed upright with every QP status 0.  det_min: inside the synthetic model's joint limits |det J_leg| reaches 0 (it changes
+ * its sign where the leg passes through its straight posture), so the limits bound nothing; within 0.5 rad of the walking loops' standing posture on every joint it stays above
+ * 1.88e-2 m^3, and 1.5e-3 leaves a factor of twelve below that.  A leg nearer to a singular posture keeps its previous bit.
+ * tests/test_contact_oracle.py holds the measured figures.
+ * Stream rules as for the ground calls: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at the buffers; a
+ * NULL required pointer (contact included): WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
+ * Out of scope: the base rows of r; a contact observer of its own; the rollout kernels and wbc_rollout_*; wbc_multi_*; the payload plant; late
+ * touchdown in the gait rule; terrain-normal footholds. */
+typedef struct wbc_contact_params {
+  size_t struct_size;     /* sizeof(wbc_contact_params) of the caller's build */
+  double f_on, f_off;     /* N; >= 0 and finite, f_off <= f_on */
+  double det_min;         /* m^3; >= 0 and finite */
+} wbc_contact_params;
+void wbc_contact_params_default(wbc_contact_params* p);
+/* a negative or non-finite value, or f_off > f_on: WBC_E_INVALID.  The values travel as a kernel argument: nothing is uploaded, later calls use them.
+ * Not inside a stream capture (a captured graph keeps the values it was captured with). */
+int wbc_solver_set_contact_params(wbc_solver* s, const wbc_contact_params* p);
+int wbc_contact_estimate_batch(wbc_solver* s, size_t N, const void* Jc, const void* r, const void* f_prev, const void* normals,
+                               int* contact /* in/out [N] */, void* f_est /* may be NULL */, void* fn_est /* may be NULL */,
+                               int* singular /* may be NULL */, void* stream);
+int wbc_gait_estimated_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r, const void* f_prev,
+                             const void* normals, int* contact /* in/out [N] */, void* phase /* in/out [N] */, int* mask /* in/out [N] */,
+                             void* swing /* in/out [36][N] */, int* events /* may be NULL, [N] */, void* f_est /* may be NULL */, void* stream);
+/* Single-robot, host-pointer, fp64 form of wbc_contact_estimate_batch (Jc[216] row-major 12 x 18, r[18], f_prev[12], normals[12] in; contact[1] in/out;
+ * the optional f_est[12], fn_est[4], singular[1] out).  Synchronises. */
+int wbc_compute_contact_estimate(wbc_solver* s, const double* Jc, const double* r, const double* f_prev, const double* normals, int* contact,
+                                 double* f_est, double* fn_est, int* singular);
+
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
  * synchronises.  obs_integ/obs_r (host, nv each) are in/out and may be NULL when the observer is off. */

@@ -278,6 +278,14 @@ def lib():
             L.wbc_solver_set_stiction_params.argtypes = [C.c_void_p, C.c_void_p]
             L.wbc_ground_stick_force_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 12
             L.wbc_integrate_ground_stick_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 16
+        # contact sensing from the observer's residual: additive to ABI 10, detected by the symbols in the same way (_contact_lib)
+        if hasattr(L, "wbc_gait_estimated_batch"):
+            L.wbc_contact_params_default.argtypes = [C.c_void_p]
+            L.wbc_contact_params_default.restype = None
+            L.wbc_solver_set_contact_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_contact_estimate_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
+            L.wbc_gait_estimated_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 14
+            L.wbc_compute_contact_estimate.argtypes = [C.c_void_p] * 9
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -336,6 +344,14 @@ def _stick_lib():
     L = lib()
     if not hasattr(L, "wbc_integrate_ground_stick_batch"):
         raise RuntimeError("%s lacks the stiction entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+def _contact_lib():
+    """lib(), for the contact-estimate calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_gait_estimated_batch"):
+        raise RuntimeError("%s lacks the contact-estimate entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     return L
 
 
@@ -462,6 +478,30 @@ class StictionParams(C.Structure):
 
     def as_dict(self):
         return dict(k_t=self.k_t)
+
+
+class ContactParams(C.Structure):
+    """wbc_contact_params: the thresholds of the contact estimate (include/wbc_hip.h, "Contact sensing from the disturbance observer")"""
+    _fields_ = [("struct_size", C.c_size_t), ("f_on", C.c_double), ("f_off", C.c_double), ("det_min", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = ContactParams()
+        _contact_lib().wbc_contact_params_default(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d):
+        """keys f_on, f_off, det_min; missing keys keep the defaults"""
+        p = ContactParams.default()
+        for k, val in d.items():
+            if k not in ("f_on", "f_off", "det_min"):
+                raise KeyError("ContactParams has no field %r" % k)
+            setattr(p, k, float(val))
+        return p
+
+    def as_dict(self):
+        return dict(f_on=self.f_on, f_off=self.f_off, det_min=self.det_min)
 
 
 GAIT_CMD_WORDS = 4   # include/wbc_hip.h: WBC_GAIT_CMD_WORDS -- cmd [GAIT_CMD_WORDS, N]: vx, vy (heading frame), wz, z_g
@@ -1102,6 +1142,65 @@ class Solver:
                                                              *self._ground_out_ptrs(N, f_gr, contact, gap), self._stream()),
                "wbc_integrate_ground_stick_batch")
         return dict(f_gr=f_gr, contact=contact, gap=gap)
+
+    def set_contact_params(self, p):
+        """p: ContactParams or dict (see ContactParams.from_dict): the thresholds of every later contact-estimate call of this solver."""
+        if isinstance(p, dict):
+            p = ContactParams.from_dict(p)
+        _check(_contact_lib().wbc_solver_set_contact_params(self._h, C.byref(p)), "wbc_solver_set_contact_params")
+
+    def _contact_in_ptrs(self, N, Jc, r, f_prev, normals, contact):
+        m = self.model
+        if contact is None:
+            raise ValueError("contact is a required in/out tensor (int32 [N]; store 0 before the first call)")
+        return (self._ptr(Jc, 3 * m.nf * m.nv, N), self._ptr(r, m.nv, N), self._ptr(f_prev, 3 * m.nf, N), self._ptr(normals, 3 * m.nf, N),
+                self._ptr(contact, 1, N, self.torch.int32))
+
+    def contact_estimate(self, Jc, r, f_prev, normals, contact, f_est=None, fn_est=None, singular=None, want_f=False, want_fn=False,
+                         want_singular=False):
+        """Foot forces and contact bits from the observer's residual (wbc_contact_estimate_batch): Jc = the last step's out["Jc"], r = the observer
+        residual after that step, f_prev = the buffer that step was given as f_prev.  contact [N] int32 advances IN PLACE (bits 0-3: in = the
+        previous estimate, out = the new one).  f_est [12, N], fn_est [4, N], singular [N] int32 are optional; want_* allocates them.  Returns
+        dict(contact, f_est, fn_est, singular)."""
+        m = self.model
+        N = Jc.shape[1]
+        if f_est is None and want_f:
+            f_est = self.empty(3 * m.nf, N)
+        if fn_est is None and want_fn:
+            fn_est = self.empty(m.nf, N)
+        if singular is None and want_singular:
+            singular = self.torch.empty(N, dtype=self.torch.int32, device=Jc.device)
+        _check(_contact_lib().wbc_contact_estimate_batch(self._h, N, *self._contact_in_ptrs(N, Jc, r, f_prev, normals, contact),
+                                                         self._ptr(f_est, 3 * m.nf, N), self._ptr(fn_est, m.nf, N),
+                                                         self._ptr(singular, 1, N, self.torch.int32), self._stream()), "wbc_contact_estimate_batch")
+        return dict(contact=contact, f_est=f_est, fn_est=fn_est, singular=singular)
+
+    def gait_estimated(self, q, v, cmd, Jc, r, f_prev, normals, contact, phase, mask, swing, events=None, f_est=None, want_f=False):
+        """contact_estimate() followed by gait(contact = the word just formed), as one launch (wbc_gait_estimated_batch): contact, phase, mask and
+        swing advance IN PLACE.  Returns dict(contact, phase, mask, swing, events, f_est)."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        if f_est is None and want_f:
+            f_est = self.empty(3 * m.nf, N)
+        _check(_contact_lib().wbc_gait_estimated_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(cmd, GAIT_CMD_WORDS, N),
+                                                       *self._contact_in_ptrs(N, Jc, r, f_prev, normals, contact), self._ptr(phase, 1, N),
+                                                       self._ptr(mask, 1, N, i32), self._ptr(swing, SWING_WORDS, N), self._ptr(events, 1, N, i32),
+                                                       self._ptr(f_est, 3 * m.nf, N), self._stream()), "wbc_gait_estimated_batch")
+        return dict(contact=contact, phase=phase, mask=mask, swing=swing, events=events, f_est=f_est)
+
+    def compute_contact_estimate(self, Jc, r, f_prev, normals, contact=0):
+        """Single-robot host-array form of contact_estimate (numpy float64, fp64 solvers; Jc [216] row-major 12 x 18): returns (contact, f_est[12],
+        fn_est[4], singular)."""
+        d = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        Jc, r, f_prev, normals = d(Jc), d(r), d(f_prev), d(normals)
+        assert Jc.size == 216 and r.size == 18 and f_prev.size == 12 and normals.size == 12
+        fe, fn = np.zeros(12), np.zeros(4)
+        cw, sg = C.c_int(int(contact)), C.c_int(0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(_contact_lib().wbc_compute_contact_estimate(self._h, p(Jc), p(r), p(f_prev), p(normals), C.byref(cw), p(fe), p(fn), C.byref(sg)),
+               "wbc_compute_contact_estimate")
+        return cw.value, fe, fn, sg.value
 
     def rollout_tracking(self, horizon, q, v, plan, normals, mu, mask, out, w_des, vdot_des, obs_integ=None, obs_r=None,
                          tau_ext=None, tau_traj=None, com_traj=None, payload=None):

@@ -256,6 +256,26 @@ template <class T> struct StickArgs {   // stick_force_kernel
   StickIO<T> s;
 };
 template <class T> struct StickIntegrateArgs : IntegrateArgs<T> { GroundIO<T> g; StickIO<T> s; };   // stick_integrate_kernel (IntegrateArgs::f is not read)
+// contact sensing from the observer's residual (contact_est.hip.hpp): the thresholds and what a call reads and writes -- BY VALUE like GroundIO
+// (wbc_solver_set_contact_params only fills the solver's host copy)
+template <class T> struct DevContactParams { T f_on, f_off, det_min; };
+template <class T> struct ContactIO {
+  const T* Jc; const T* r; const T* f_prev; const T* normals;   // [3 nf nv][N], [nv][N], [12][N], [12][N]
+  int* contact;    // [N] in/out: bits 0-3
+  T* f_est;        // [12][N] or null
+  T* fn_est;       // [4][N] or null
+  int* singular;   // [N] or null
+  DevContactParams<T> P;
+};
+template <class T> struct ContactArgs {   // contact_estimate_kernel
+  size_t N;
+  unsigned long long jpack;   // see SweepArgs::jpack
+  ContactIO<T> c;
+};
+template <class T> struct GaitEstimatedArgs {   // gait_estimated_kernel: g.contact is not read (the word arrives in registers)
+  GaitArgs<T> g;
+  ContactIO<T> c;
+};
 
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc

@@ -142,5 +142,10 @@ template <class T> hipError_t k_ground_integrate(const LaunchCtx& L, const DevMo
 // place); stick_integrate_kernel<T> is that law followed by k_integrate with f = f_gr handed over in registers -- one launch
 template <class T> hipError_t k_stick_force(const LaunchCtx& L, const DevModel<T>* model, const StickArgs<T>& a);
 template <class T> hipError_t k_stick_integrate(const LaunchCtx& L, const DevModel<T>* model, const StickIntegrateArgs<T>& a);
+// contact sensing from the observer's residual (contact_est.hip.hpp): contact_estimate_kernel<T> is the law alone (f_est, fn_est, singular and the
+// contact word, in place, from Jc, r, f_prev and the normals); gait_estimated_kernel<T> is the same law followed by k_gait with the word handed over in
+// registers -- one launch
+template <class T> hipError_t k_contact_estimate(const LaunchCtx& L, const DevModel<T>* model, const ContactArgs<T>& a);
+template <class T> hipError_t k_gait_estimated(const LaunchCtx& L, const DevModel<T>* model, const GaitEstimatedArgs<T>& a);
 
 }  // namespace wbc

@@ -60,6 +60,7 @@ constexpr int ONE_SCRATCH = 200;        // first scalar of the helpers' scratch 
 constexpr int ONE_SCALARS = 288;        // scalars in front of the image's ints (the tick uses the first 161)
 constexpr int SWING_ONE_SCALARS = 19 + 18 + 36 + 18 + 24;   // wbc_compute_swing_reference: q v swing | vdot_des | foot, then one int (the mask)
 constexpr int GAIT_ONE_SCALARS = 19 + 18 + 4 + 1 + 36;      // wbc_compute_gait: q v cmd | phase swing, then three ints (contact, mask, events)
+constexpr int CONTACT_ONE_SCALARS = 216 + 18 + 12 + 12 + 12 + 4;   // wbc_compute_contact_estimate: Jc r f_prev normals | f_est fn_est, then two ints (contact, singular)
 
 // thresholds between kernel variants after the options are applied (resolve_options)
 constexpr long long WBC_OBS_SPLIT_MIN_NOMATS_F64 = 16384;
@@ -98,6 +99,8 @@ struct wbc_solver {
   wbc_stiction_params stiction;  // the anchor spring of the ground plant's stiction calls (wbc_solver_set_stiction_params; a kernel argument by value)
   wbc_gait_params gait;      // the schedule of the gait scheduler (wbc_solver_set_gait_params; kernel arguments by value), the model's defaults at creation
   void* d_gait_one = nullptr;    // wbc_compute_gait's staging: GAIT_ONE_SCALARS scalars + contact, mask, events
+  wbc_contact_params contact_est;   // the thresholds of the contact estimate (wbc_solver_set_contact_params; a kernel argument by value), the defaults at creation
+  void* d_contact_one = nullptr;    // wbc_compute_contact_estimate's staging: CONTACT_ONE_SCALARS scalars + contact, singular
   // torque-limit post-pass (wbc_limit_torques_batch): the limits travel as a kernel argument like the score weights
   double tau_max[WBC_MAXV];  // caller's joint order, HUGE_VAL = none; the model's effort limits at creation
   double model_effort[WBC_MAXV];
@@ -655,6 +658,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   wbc_gait_params_default(m, &s->gait);
   wbc_ground_params_default(&s->ground);
   wbc_stiction_params_default(&s->stiction);
+  wbc_contact_params_default(&s->contact_est);
   for (int j = 0; j < WBC_MAXV; ++j) s->model_effort[j] = (j < m->fm.nj() && j < (int)m->fm.effort_limit.size()) ? m->fm.effort_limit[j] : HUGE_VAL;
   std::memcpy(s->tau_max, s->model_effort, sizeof(s->tau_max));
   s->limit_grid = limit_qp_grid(prop.multiProcessorCount);
@@ -694,6 +698,7 @@ extern "C" int wbc_solver_create_ex(const wbc_model* m, const wbc_params* p, int
   if (e == hipSuccess) { std::memset(s->h_one, 0, s->one_bytes); e = hipMemset(s->d_one, 0, s->one_bytes); }
   if (e == hipSuccess) e = hipMalloc(&s->d_swing_one, SWING_ONE_SCALARS * sizeof(double) + sizeof(int));
   if (e == hipSuccess) e = hipMalloc(&s->d_gait_one, GAIT_ONE_SCALARS * sizeof(double) + 3 * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&s->d_contact_one, CONTACT_ONE_SCALARS * sizeof(double) + 2 * sizeof(int));
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->aux, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming);
@@ -727,6 +732,7 @@ extern "C" void wbc_solver_destroy(wbc_solver* s) {
   if (s->d_ref) (void)hipFree(s->d_ref);
   if (s->d_swing_one) (void)hipFree(s->d_swing_one);
   if (s->d_gait_one) (void)hipFree(s->d_gait_one);
+  if (s->d_contact_one) (void)hipFree(s->d_contact_one);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);
   if (s->aux) (void)hipStreamDestroy(s->aux);
@@ -1516,6 +1522,23 @@ extern "C" int wbc_solver_set_gait_params(wbc_solver* s, const wbc_gait_params* 
   return WBC_OK;
 }
 
+// (the caller has zeroed `a`; shared with wbc_gait_estimated_batch, which forms the contact word in the same launch and passes contact = null)
+template <class T>
+static void gait_args(GaitArgs<T>& a, const wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact, void* phase,
+                      int* mask, void* swing, int* events) {
+  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.cmd = (const T*)cmd; a.contact = contact;
+  a.phase = (T*)phase; a.mask = mask; a.swing = (T*)swing; a.events = events; a.jpack = s->jpack;
+  const wbc_gait_params& g = s->gait;
+  a.P.dphi = (T)(s->params.dt / g.period); a.P.period = (T)g.period; a.P.clearance = (T)g.clearance; a.P.k_v = (T)g.k_v; a.P.late = (T)g.late;
+  for (int k = 0; k < 4; ++k) {
+    a.P.duty[k] = (T)g.duty[k]; a.P.offset[k] = (T)g.offset[k];
+    a.P.inv_sw[k] = g.duty[k] == 1.0 ? (T)0 : (T)(1.0 / (1.0 - g.duty[k]));
+    a.P.T_sw[k] = (T)((1.0 - g.duty[k]) * g.period);
+    a.P.bx[k] = (T)g.base_xy[k][0]; a.P.by[k] = (T)g.base_xy[k][1];
+  }
+  a.P.retarget = g.retarget;
+}
+
 extern "C" int wbc_gait_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact, void* phase, int* mask,
                               void* swing, int* events, void* stream) {
   if (!s) return fail(WBC_E_INVALID, "null solver");
@@ -1525,17 +1548,7 @@ extern "C" int wbc_gait_batch(wbc_solver* s, size_t N, const void* q, const void
     using T = decltype(scalar);
     GaitArgs<T> a;
     std::memset(&a, 0, sizeof(a));
-    a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.cmd = (const T*)cmd; a.contact = contact;
-    a.phase = (T*)phase; a.mask = mask; a.swing = (T*)swing; a.events = events; a.jpack = s->jpack;
-    const wbc_gait_params& g = s->gait;
-    a.P.dphi = (T)(s->params.dt / g.period); a.P.period = (T)g.period; a.P.clearance = (T)g.clearance; a.P.k_v = (T)g.k_v; a.P.late = (T)g.late;
-    for (int k = 0; k < 4; ++k) {
-      a.P.duty[k] = (T)g.duty[k]; a.P.offset[k] = (T)g.offset[k];
-      a.P.inv_sw[k] = g.duty[k] == 1.0 ? (T)0 : (T)(1.0 / (1.0 - g.duty[k]));
-      a.P.T_sw[k] = (T)((1.0 - g.duty[k]) * g.period);
-      a.P.bx[k] = (T)g.base_xy[k][0]; a.P.by[k] = (T)g.base_xy[k][1];
-    }
-    a.P.retarget = g.retarget;
+    gait_args(a, s, N, q, v, cmd, contact, phase, mask, swing, events);
     return k_gait<T>(L, dev_model<T>(s), a);
   });
 }
@@ -1646,6 +1659,64 @@ extern "C" int wbc_integrate_ground_stick_batch(wbc_solver* s, size_t N, void* q
     ground_io(a.g, s, normals, height, mu, f_gr, contact, gap);
     stick_io(a.s, s, anchor, stick);
     return k_stick_integrate<T>(L, dev_model<T>(s), a);
+  });
+}
+
+// ---- contact sensing from the observer's residual: the thresholds, the law alone, the law + the gait scheduler as one launch
+extern "C" void wbc_contact_params_default(wbc_contact_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->f_on = 15.0; p->f_off = 5.0; p->det_min = 1.5e-3;   // how they were fixed: include/wbc_hip.h
+}
+
+extern "C" int wbc_solver_set_contact_params(wbc_solver* s, const wbc_contact_params* p) {
+  if (!s || !p) return fail(WBC_E_INVALID, "null argument");
+  if (p->struct_size < sizeof(wbc_contact_params)) return fail(WBC_E_INVALID, "wbc_contact_params: struct_size too small (call wbc_contact_params_default first)");
+  const double val[3] = {p->f_on, p->f_off, p->det_min};
+  for (int i = 0; i < 3; ++i)
+    if (!(val[i] >= 0) || !std::isfinite(val[i])) return fail(WBC_E_INVALID, "wbc_contact_params: f_on, f_off, det_min must be finite and >= 0");
+  if (p->f_off > p->f_on) return fail(WBC_E_INVALID, "wbc_contact_params: f_off must not exceed f_on");
+  s->contact_est = *p;
+  return WBC_OK;
+}
+
+template <class T>
+static void contact_io(ContactIO<T>& c, const wbc_solver* s, const void* Jc, const void* r, const void* f_prev, const void* normals, int* contact,
+                       void* f_est, void* fn_est, int* singular) {
+  c.Jc = (const T*)Jc; c.r = (const T*)r; c.f_prev = (const T*)f_prev; c.normals = (const T*)normals;
+  c.contact = contact; c.f_est = (T*)f_est; c.fn_est = (T*)fn_est; c.singular = singular;
+  c.P.f_on = (T)s->contact_est.f_on; c.P.f_off = (T)s->contact_est.f_off; c.P.det_min = (T)s->contact_est.det_min;
+}
+
+extern "C" int wbc_contact_estimate_batch(wbc_solver* s, size_t N, const void* Jc, const void* r, const void* f_prev, const void* normals, int* contact,
+                                          void* f_est, void* fn_est, int* singular, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!Jc || !r || !f_prev || !normals || !contact) return fail(WBC_E_INVALID, "null argument");
+  return launch_batch(s, N, stream, "contact estimate", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    ContactArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.jpack = s->jpack;
+    contact_io(a.c, s, Jc, r, f_prev, normals, contact, f_est, fn_est, singular);
+    return k_contact_estimate<T>(L, dev_model<T>(s), a);
+  });
+}
+
+extern "C" int wbc_gait_estimated_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r,
+                                        const void* f_prev, const void* normals, int* contact, void* phase, int* mask, void* swing, int* events,
+                                        void* f_est, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !Jc || !r || !f_prev || !normals || !contact || !phase || !mask || !swing) return fail(WBC_E_INVALID, "null argument");
+  return launch_batch(s, N, stream, "gait estimated", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GaitEstimatedArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    gait_args(a.g, s, N, q, v, cmd, nullptr, phase, mask, swing, events);
+    contact_io(a.c, s, Jc, r, f_prev, normals, contact, f_est, nullptr, nullptr);
+    return k_gait_estimated<T>(L, dev_model<T>(s), a);
   });
 }
 
@@ -1928,6 +1999,32 @@ extern "C" int wbc_compute_gait(wbc_solver* s, const double* q, const double* v,
   *phase = h[op]; std::memcpy(swing, h + os, SWING_WORDS * sizeof(double));
   *mask = hi[1];
   if (events) *events = hi[2];
+  return WBC_OK;
+}
+
+// Single-robot, host-pointer form of wbc_contact_estimate_batch: staged through the solver's own device block like wbc_compute_gait.
+extern "C" int wbc_compute_contact_estimate(wbc_solver* s, const double* Jc, const double* r, const double* f_prev, const double* normals, int* contact,
+                                            double* f_est, double* fn_est, int* singular) {
+  if (!s || !Jc || !r || !f_prev || !normals || !contact) return fail(WBC_E_INVALID, "null argument");
+  if (s->dtype != WBC_F64) return fail(WBC_E_INVALID, "wbc_compute_contact_estimate: fp64 solvers only");
+  ON_DEVICE(s);
+  double h[CONTACT_ONE_SCALARS];
+  const int oj = 0, orr = 216, ofp = 234, on = 246, ofe = 258, ofn = 270;
+  std::memcpy(h + oj, Jc, 216 * sizeof(double)); std::memcpy(h + orr, r, 18 * sizeof(double));
+  std::memcpy(h + ofp, f_prev, 12 * sizeof(double)); std::memcpy(h + on, normals, 12 * sizeof(double));
+  int hi[2] = {*contact, 0};
+  double* d = (double*)s->d_contact_one;
+  int* di = (int*)(d + CONTACT_ONE_SCALARS);
+  HIP_TRY(hipMemcpy(d, h, ofe * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(di, hi, sizeof(hi), hipMemcpyHostToDevice));
+  int rc = wbc_contact_estimate_batch(s, 1, d + oj, d + orr, d + ofp, d + on, di, d + ofe, d + ofn, di + 1, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(h + ofe, d + ofe, 16 * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hi, di, sizeof(hi), hipMemcpyDeviceToHost));
+  *contact = hi[0];
+  if (f_est) std::memcpy(f_est, h + ofe, 12 * sizeof(double));
+  if (fn_est) std::memcpy(fn_est, h + ofn, 4 * sizeof(double));
+  if (singular) *singular = hi[1];
   return WBC_OK;
 }
 
