@@ -10,7 +10,7 @@ contact [N] int32; `legs` = limit_ref.leg_joints(flat), the caller's joint indic
 """
 import numpy as np
 
-from tests import gait_ref as GR, ground_ref as GND, limit_ref, swing_ref as SR
+from tests import gait_ref as GR, ground_ref as GND, limit_ref, swing_ref as SR, walk_ref
 from wbc_quadruped_dob_amd import synth
 
 # wbc_contact_params_default.  Fixed with closed_loop() below (observer_order 1, K1 = 50, dt = 2^-10; tests/test_contact_oracle.py holds the figures).
@@ -249,46 +249,22 @@ def closed_loop(flat, oracle, case, sensed="estimate", ticks=GND.WALK_TICKS, P=N
     |fn - threshold in force| / max |fn| over all regular feet and ticks; singular_any)"""
     assert sensed in ("estimate", "truth", "none")
     P = P or params()
-    GPp = GP_ground or GND.params()
     GP = GR.walk_params(flat)
-    prm, G = synth.default_params(observer_order=1), SR.loop_ref_params()
-    prm["dt"] = GR.DYADIC_DT
-    legs = limit_ref.leg_joints(flat)
-    q, v = (case["q"] if q0 is None else q0).copy(), case["v"].copy()
-    n = q.shape[0]
-    phase, mask, swing = case["phase"].copy(), case["mask"].copy(), case["swing"].copy()
-    integ = np.ascontiguousarray(oracle.dynamics(q, v)["p"])
-    r = np.zeros((n, 18))
-    tau_prev, f_prev = np.zeros((n, 12)), np.zeros((n, 12))
-    est = np.zeros(n, np.int32)
-    truth = np.zeros(n, np.int32)
-    rec = dict(masks=[], events=[], contacts=[], truth=[], phases=[], fn_est=[], fn_true=[], thr=[])
-    ok, sing_any = True, False
-    for k in range(ticks):
-        word = dict(estimate=est, truth=truth, none=None)[sensed]
-        phase, mask, swing, ev = GR.gait_tick(flat, GP, prm["dt"], q, v, case["cmd"], word, phase, mask, swing)
-        ref = oracle.reference(G, q, v, case["plan"], k * prm["dt"])
-        vd, _ = SR.swing_reference(flat, q, v, mask, swing, 0.0, ref["vdot_des"], GR.WALK_SWING_PARAMS)
-        tick = oracle.step(prm, q, v, ref["w_des"], vd, case["normals"], case["mu"], mask, tau_prev, f_prev, integ, r)
-        ok = ok and bool(np.all(tick["status"] == 0))
-        dyn = oracle.dynamics(q, v)
-        e = estimate(P, dyn["Jc"], r, f_prev, case["normals"], est, legs)
-        was = ((est[:, None] >> np.arange(4)[None, :]) & 1) == 1
+    rec = dict(fn_est=[], fn_true=[], thr=[], singular=[])
+
+    def extras(now):
+        e = now["estimate"]
+        was = ((e["prev"][:, None] >> np.arange(4)[None, :]) & 1) == 1
         rec["thr"].append(np.abs(e["fn"] - np.where(was, P["f_off"], P["f_on"])))
-        est = e["contact"]
-        sing_any = sing_any or bool(e["singular"].any())
-        tau_prev, f_prev = tick["tau"], tick["f"]
-        height = case["height0"] if k < GND.BUMP_TICK else case["height1"]
-        q, v, g = GND.integrate_ground(GPp, prm["dt"], dyn, tick["tau"], case["normals"], height, case["mu"], None, q, v, legs)
-        truth = g["contact"]
-        for key, val in (("masks", mask), ("events", ev), ("contacts", est), ("truth", truth), ("phases", phase), ("fn_est", e["fn"]),
-                         ("fn_true", g["fn"])):
-            rec[key].append(val.copy())
+        rec["fn_est"].append(e["fn"].copy()); rec["fn_true"].append(now["ground"]["fn"].copy()); rec["singular"].append(e["singular"])
+
+    w = walk_ref.closed_loop(flat, oracle, case, ticks, walk_ref.ground_plant(flat, case, GP_ground or GND.params()), GR.WALK_SWING_PARAMS, gait=GP,
+                             sensed=dict(estimate="estimate", truth="plant", none=None)[sensed], observer=P, q0=q0, extras=extras)
     rec = {key: np.array(val) for key, val in rec.items()}
-    out = dict(q=q, v=v, status_ok=ok, singular_any=sing_any, early=GND.early_touchdowns(GP, rec["phases"], rec["events"]),
-               thr_margin=float(rec["thr"].min() / np.abs(rec["fn_est"]).max()), fn_max=float(np.abs(rec["fn_est"]).max()))
-    out.update({key: rec[key] for key in ("masks", "events", "contacts", "truth", "phases", "fn_est", "fn_true")})
-    return out
+    return dict(q=w["q"], v=w["v"], status_ok=w["status_ok"], singular_any=bool(rec["singular"].any()),
+                early=GND.early_touchdowns(GP, w["phases"], w["events"]), thr_margin=float(rec["thr"].min() / np.abs(rec["fn_est"]).max()),
+                fn_max=float(np.abs(rec["fn_est"]).max()), masks=w["masks"], events=w["events"], contacts=w["estimates"], truth=w["contacts"],
+                phases=w["phases"], fn_est=rec["fn_est"], fn_true=rec["fn_true"])
 
 
 def toggles(contacts):
@@ -305,13 +281,6 @@ def first_early(early, state, foot, after=GND.BUMP_TICK):
     return min(t) if t else None
 
 
-_WALKS = {}
-
-
 def cpu_walk(flat, oracle, sensed="estimate", n=WALK_N):
     """(case, closed_loop(case, sensed)) of n robots, computed once per process and shared by the tests that need it: read only"""
-    key = (id(flat), n, sensed)
-    if key not in _WALKS:
-        case = GND.walk_case(flat, oracle, n)
-        _WALKS[key] = (case, closed_loop(flat, oracle, case, sensed))
-    return _WALKS[key]
+    return walk_ref.cached(("contact", id(flat), n, sensed), lambda: GND.walk_case(flat, oracle, n), lambda case: closed_loop(flat, oracle, case, sensed))

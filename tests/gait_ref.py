@@ -10,7 +10,7 @@ single precision costs (tests/test_gpu_gait.py, F32_GATE).  Row-per-state arrays
 """
 import numpy as np
 
-from tests import limit_ref, swing_ref as SR
+from tests import swing_ref as SR, walk_ref
 from wbc_quadruped_dob_amd import synth
 
 DEFAULT_PARAMS = dict(period=0.4, duty=(0.6,) * 4, offset=(0.0, 0.5, 0.5, 0.0), clearance=0.05, k_v=0.03, late=0.5, retarget=1)
@@ -240,35 +240,16 @@ def closed_loop(flat, oracle, case, ticks=WALK_TICKS, P=None, swing_params=None)
     every touchdown, p_f the foot position the gait call of that tick saw)."""
     P = P or walk_params(flat)
     swing_params = WALK_SWING_PARAMS if swing_params is None else swing_params
-    prm, G = synth.default_params(observer_order=0), SR.loop_ref_params()
-    prm["dt"] = DYADIC_DT
-    q, v = case["q"].copy(), case["v"].copy()
-    phase, mask, swing = case["phase"].copy(), case["mask"].copy(), case["swing"].copy()
-    masks, events, landings, ok = [], [], [], True
-    for k in range(ticks):
-        phase, mask, swing, ev = gait_tick(flat, P, prm["dt"], q, v, case["cmd"], None, phase, mask, swing)
-        masks.append(mask.copy()); events.append(ev.copy())
-        landings += landings_of(flat, k, q, v, swing, ev)
-        ref = oracle.reference(G, q, v, case["plan"], k * prm["dt"])
-        vd, _ = SR.swing_reference(flat, q, v, mask, swing, 0.0, ref["vdot_des"], swing_params)
-        tick = oracle.step(prm, q, v, ref["w_des"], vd, case["normals"], case["mu"], mask)
-        ok = ok and bool(np.all(tick["status"] == 0))
-        dyn = oracle.dynamics(q, v)
-        limit_ref.integrate(prm, dyn, tick["tau"], tick["f"], q, v)
-    foot = np.concatenate([np.concatenate([K["pf"], K["Jv"]], 1) for K in (SR.foot_kin(flat, k, q, v) for k in range(4))], 1)
-    return dict(q=q, v=v, foot=foot, masks=np.array(masks), events=np.array(events), status_ok=ok, landings=landings, phase=phase, swing=swing)
-
-
-_WALKS = {}
+    landings = []
+    extras = lambda now: landings.extend(landings_of(flat, now["k"], now["q"], now["v"], now["swing"], now["events"]))
+    w = walk_ref.closed_loop(flat, oracle, case, ticks, walk_ref.rigid_plant(), swing_params, gait=P, extras=extras)
+    return dict(q=w["q"], v=w["v"], foot=SR.foot_words(flat, w["q"], w["v"]), masks=w["masks"], events=w["events"], status_ok=w["status_ok"],
+                landings=landings, phase=w["phase"], swing=w["swing"])
 
 
 def cpu_walk(flat, oracle, n):
     """(case, closed_loop(case)) of n robots, computed once per process and shared by the tests that need it: read only"""
-    key = (id(flat), n)
-    if key not in _WALKS:
-        case = walk_case(flat, oracle, n)
-        _WALKS[key] = (case, closed_loop(flat, oracle, case))
-    return _WALKS[key]
+    return walk_ref.cached(("gait", id(flat), n), lambda: walk_case(flat, oracle, n), lambda case: closed_loop(flat, oracle, case))
 
 
 def landing_ratios(landings, min_step=0.02):

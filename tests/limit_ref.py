@@ -4,6 +4,7 @@ it with the torque rows added.  Test infrastructure: row-per-state arrays like e
 import numpy as np
 
 from oracle import oracle_py
+from tests import payload_ref
 from wbc_quadruped_dob_amd import synth
 
 
@@ -134,16 +135,7 @@ def integrate(P, dyn, tau, f, q, v):
         J = dyn["Jc"][s].reshape(-1, nv)
         rhs = -dyn["h"][s] + J.T @ f[s]
         rhs[6:] += tau[s]
-        v[s] += dt * np.linalg.solve(M, rhs)
-        q[s, :3] += dt * v[s, :3]
-        w = v[s, 3:6] * dt
-        th = np.sqrt(w @ w)
-        sc, cw = (np.sin(th / 2) / th, np.cos(th / 2)) if th > 1e-8 else (0.5 - th * th / 48, 1 - th * th / 8)
-        dx, dy, dz = sc * w
-        x, y, z, ww = q[s, 3:7] / np.linalg.norm(q[s, 3:7])
-        q[s, 3:7] = [cw * x + dx * ww + dy * z - dz * y, cw * y - dx * z + dy * ww + dz * x, cw * z + dx * y - dy * x + dz * ww,
-                     cw * ww - dx * x - dy * y - dz * z]
-        q[s, 7:] += dt * v[s, 6:]
+        q[s], v[s] = payload_ref.integrate_state(q[s], v[s], np.linalg.solve(M, rhs), dt)
 
 
 def swing_case(total_mass, n=64, legs=None):

@@ -13,8 +13,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests import contact_ref as R, gait_ref as GR, ground_ref as GND, limit_models, limit_ref, swing_ref as SR
-from tests.util import elementwise_excess, relerr, to_dev, to_host
+from tests import contact_ref as R, gait_ref as GR, ground_ref as GND, limit_models, limit_ref, walk_dev as WD
+from tests.util import elementwise_excess, relerr, to_dev, to_host, torch_dtype as _td
 from wbc_quadruped_dob_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -28,25 +28,7 @@ def torch_cuda():
     return torch
 
 
-def _solver(model, dtype="f64", max_batch=64, dt=None, observer=1, contact=None, ref_params=None, gait=None, swing=None):
-    import wbc_quadruped_dob_amd as W
-    P = synth.default_params(observer_order=observer, dtype=dtype)
-    if dt is not None:
-        P["dt"] = dt
-    s = W.Solver(model, W.Params.from_dict(P, dtype), dtype=dtype, device=0, max_batch=max_batch)
-    if contact is not None:
-        s.set_contact_params(contact)
-    if ref_params is not None:
-        s.set_ref_params(ref_params)
-    if gait is not None:
-        s.set_gait_params({k: (np.asarray(v) if k in ("duty", "offset", "base_xy") else v) for k, v in gait.items()})
-    if swing is not None:
-        s.set_swing_params(swing)
-    return s
-
-
-def _td(torch, dtype):
-    return torch.float64 if dtype == "f64" else torch.float32
+_solver = functools.partial(WD.solver, observer=1)
 
 
 _FLATS = {}
@@ -257,54 +239,15 @@ def test_argument_checks_through_the_binding(torch_cuda, gpu_model):
     assert W.ContactParams.default().as_dict() == R.DEFAULT_PARAMS
 
 
-# ---- the estimated walking tick: gait_estimated -> reference_swing -> step (observer on) -> integrate_ground
-# Which buffers belong together: gait_estimated reads the Jc the LAST step wrote, the r that step left, and the buffer that step
-# was GIVEN as f_prev.  The step of this tick is given the f the last step WROTE, so tau / f alternate between two buffer pairs: the step of tick k
-# reads pair k % 2 as tau_prev, f_prev and writes pair (k + 1) % 2 -- the pair the step of tick k - 1 was given, which gait_estimated of tick k has
-# read by then.
-def _walk_solver(model, flat, n, dtype="f64"):
-    return _solver(model, dtype, max_batch=n, dt=GR.DYADIC_DT, ref_params=SR.loop_ref_params(), gait=GR.walk_params(flat), swing=GR.WALK_SWING_PARAMS)
+# ---- the estimated walking tick: gait_estimated -> reference_swing -> step (observer on) -> integrate_ground (walk_dev.tick, which says which
+# buffers belong together)
+WALK = dict(plant="ground", sense="estimate")
 
 
-def _walk_dev(torch, solver, case):
-    td = torch.float64
-    d = {k: to_dev(case[k], torch, td) for k in ("cmd", "plan", "normals", "mu", "height0", "height1")}
-    n = case["q"].shape[0]
-    e = lambda r: torch.zeros((r, n), dtype=td, device="cuda")
-    i = lambda: torch.zeros(n, dtype=torch.int32, device="cuda")
-    d["ref"] = dict(w_des=e(6), vdot_des=e(18))
-    d["mats"] = dict(M=e(171), h=e(18), Jc=e(216), pf=e(12))
-    d["status"], d["iters"] = i(), i()
-    d["events"], d["f_gr"], d["plant_contact"], d["height"] = i(), e(12), i(), d["height0"].clone()
-    return d
-
-
-def _walk_state(torch, solver, case):
-    """what a tick advances: q, v, phase, mask, swing, the estimated word, the observer state and the two tau / f pairs"""
-    td = torch.float64
-    n = case["q"].shape[0]
-    e = lambda r: torch.zeros((r, n), dtype=td, device="cuda")
-    st = dict(q=to_dev(case["q"], torch, td), v=to_dev(case["v"], torch, td), phase=torch.from_numpy(case["phase"]).to(td).cuda(),
-              mask=torch.from_numpy(case["mask"]).to(torch.int32).cuda(), swing=to_dev(case["swing"], torch, td),
-              contact=torch.zeros(n, dtype=torch.int32, device="cuda"), r=e(18), tau0=e(12), f0=e(12), tau1=e(12), f1=e(12))
-    st["integ"] = solver.dynamics(st["q"], st["v"], want=("p",))["p"]          # the observer starts at p(0) = M v
-    return st
-
-
-def _tick(solver, d, st, k, first=False):
-    """Walking tick k on the state st; no host work between the four launches.  The first tick of a loop has no step behind it: plain gait()."""
-    a, b = str(k % 2), str((k + 1) % 2)
-    if first:
-        solver.gait(st["q"], st["v"], d["cmd"], st["phase"], st["mask"], st["swing"], contact=None, events=d["events"])
-    else:
-        solver.gait_estimated(st["q"], st["v"], d["cmd"], d["mats"]["Jc"], st["r"], st["f" + b], d["normals"], st["contact"], st["phase"], st["mask"],
-                              st["swing"], events=d["events"])
-    solver.reference_swing(st["q"], st["v"], d["plan"], st["mask"], st["swing"], 0.0, out=d["ref"])
-    out = dict(d["mats"], tau=st["tau" + b], f=st["f" + b], status=d["status"], iters=d["iters"])
-    solver.step(st["q"], st["v"], d["ref"]["w_des"], d["ref"]["vdot_des"], d["normals"], d["mu"], st["mask"], tau_prev=st["tau" + a], f_prev=st["f" + a],
-                obs_integ=st["integ"], obs_r=st["r"], out=out, want_mats=True)
-    solver.integrate_ground(st["q"], st["v"], d["mats"]["M"], d["mats"]["h"], d["mats"]["Jc"], st["tau" + b], d["normals"], d["height"], d["mu"],
-                            f_gr=d["f_gr"], contact=d["plant_contact"])
+def _walk(torch, model, flat, case):
+    """solver, buffers and state of the estimated walking loop"""
+    solver = WD.walk_solver(model, flat, case["q"].shape[0], observer=1)
+    return solver, WD.buffers(torch, case, "ground", observer=True), WD.state(torch, case, "ground", observer=solver)
 
 
 @functools.lru_cache(maxsize=None)
@@ -323,18 +266,16 @@ def test_gait_estimated_equals_contact_estimate_then_gait(torch_cuda, gpu_model,
     torch = torch_cuda
     _FLATS["walk"] = (flat_model, oracle)
     case = _walk_case(n)
-    solver = _walk_solver(gpu_model, flat_model, n)
-    s32 = _walk_solver(gpu_model, flat_model, n, "f32")
-    d = _walk_dev(torch, solver, case)
-    st = _walk_state(torch, solver, case)
+    solver, d, st = _walk(torch, gpu_model, flat_model, case)
+    s32 = WD.walk_solver(gpu_model, flat_model, n, "f32", observer=1)
+    swap = WD.terrain_swap(d)
     sensed_mattered = False
     for k in range(FUSED_FROM + FUSED_TICKS):
-        if k == GND.BUMP_TICK:
-            d["height"].copy_(d["height1"])
+        swap(k)
         if k >= FUSED_FROM:
             for sv, td in ((solver, torch.float64), (s32, torch.float32)):
                 cv = lambda t: t.to(td).contiguous() if t.dtype.is_floating_point else t.clone()
-                ins = [cv(x) for x in (st["q"], st["v"], d["cmd"], d["mats"]["Jc"], st["r"], st["f" + str((k + 1) % 2)], d["normals"])]
+                ins = [cv(x) for x in (st["q"], st["v"], d["cmd"], d["tick"]["Jc"], st["r"], st["f" + str((k + 1) % 2)], d["normals"])]
                 one = dict(contact=st["contact"].clone(), phase=cv(st["phase"]), mask=st["mask"].clone(), swing=cv(st["swing"]),
                            events=torch.full_like(d["events"], -1), f_est=torch.full((12, n), 7.5, dtype=td, device="cuda"))
                 two = {key: x.clone() for key, x in one.items()}
@@ -347,9 +288,9 @@ def test_gait_estimated_equals_contact_estimate_then_gait(torch_cuda, gpu_model,
                 for key in one:
                     assert torch.equal(one[key], two[key]), (key, k, str(td))
                 sensed_mattered = sensed_mattered or not torch.equal(one["mask"], blind["mask"])
-        _tick(solver, d, st, k, first=(k == 0))
+        WD.tick(solver, d, st, k=k, first=(k == 0), **WALK)
     torch.cuda.synchronize()
-    assert bool((d["status"] == 0).all())
+    assert bool((d["tick"]["status"] == 0).all())
     assert sensed_mattered          # robot 0 stands over a bump: its early touchdown falls in these ticks
 
 
@@ -362,17 +303,15 @@ def test_captured_walking_tick_replays_bit_for_bit(torch_cuda, gpu_model, flat_m
     n = 17
     _FLATS["walk"] = (flat_model, oracle)
     case = _walk_case(n)
-    solver = _walk_solver(gpu_model, flat_model, n)
-    d = _walk_dev(torch, solver, case)
+    solver, d, start = _walk(torch, gpu_model, flat_model, case)
     d["height"] += 1e-3
-    start = _walk_state(torch, solver, case)
-    _tick(solver, d, start, 0, first=True)
-    _tick(solver, d, start, 1)
+    WD.tick(solver, d, start, k=0, first=True, **WALK)
+    WD.tick(solver, d, start, k=1, **WALK)
     torch.cuda.synchronize()
-    Jc2 = d["mats"]["Jc"].clone()          # the matrices the second tick left: gait_estimated of the next tick reads Jc
+    Jc2 = d["tick"]["Jc"].clone()          # the matrices the second tick left: gait_estimated of the next tick reads Jc
     st = {k: x.clone() for k, x in start.items()}
     for k in range(2, 10):
-        _tick(solver, d, st, k)
+        WD.tick(solver, d, st, k=k, **WALK)
     torch.cuda.synchronize()
     assert bool((st["contact"] != 0).all()) and bool((st["r"] != 0).any())
     eager = {k: x.clone() for k, x in st.items()}
@@ -381,26 +320,14 @@ def test_captured_walking_tick_replays_bit_for_bit(torch_cuda, gpu_model, flat_m
     def rewind():
         for k in st:
             st[k].copy_(start[k])
-        d["mats"]["Jc"].copy_(Jc2)
+        d["tick"]["Jc"].copy_(Jc2)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):   # warm-up on the side stream (torch's capture recipe)
-        rewind()
-        _tick(solver, d, st, 2)
-        _tick(solver, d, st, 3)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    rewind()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        _tick(solver, d, st, 2)
-        _tick(solver, d, st, 3)
-    solver.set_contact_params(dict(f_on=1e5, f_off=1e5))   # a captured graph keeps the thresholds it was captured with
-    rewind()
-    for _ in range(4):
-        g.replay()
-    torch.cuda.synchronize()
+    def two_ticks():
+        WD.tick(solver, d, st, k=2, **WALK)
+        WD.tick(solver, d, st, k=3, **WALK)
+
+    WD.capture_replay(torch, two_ticks, rewind, 4,
+                      lambda: solver.set_contact_params(dict(f_on=1e5, f_off=1e5)))   # a captured graph keeps the thresholds it was captured with
     for k in st:
         assert torch.equal(st[k], eager[k]), k
     assert torch.equal(d["f_gr"], eager["f_gr"]) and bool((d["f_gr"] != 0).any())
@@ -417,27 +344,17 @@ def test_closed_loop_matches_the_cpu_loop(torch_cuda, gpu_model, flat_model, ora
     assert cpu["status_ok"] and all(R.first_early(cpu["early"], s, 1) is not None for s in range(0, n, 2))
     gate = max(1e-6, 10 * R.WALK_AMPLIFICATION * 1e-9)
     assert gate <= 1e-3
-    solver = _walk_solver(gpu_model, flat_model, n)
-    d = _walk_dev(torch, solver, case)
-    st = _walk_state(torch, solver, case)
-    rec = {k: torch.zeros((ticks, n), dtype=torch.int32, device="cuda") for k in ("mask", "events", "contact", "status")}
-    phases = torch.zeros((ticks, n), dtype=torch.float64, device="cuda")
-    for k in range(ticks):
-        d["plan"][7] = k * GR.DYADIC_DT                   # the CoM plan's elapsed time (a fill on the stream, no synchronisation)
-        if k == GND.BUMP_TICK:
-            d["height"].copy_(d["height1"])
-        _tick(solver, d, st, k, first=(k == 0))
-        rec["mask"][k].copy_(st["mask"]); rec["events"][k].copy_(d["events"]); rec["contact"][k].copy_(st["contact"])
-        rec["status"][k].copy_(d["status"]); phases[k].copy_(st["phase"])
+    solver, d, st = _walk(torch, gpu_model, flat_model, case)
+    rec = WD.run_loop(torch, d, ticks, lambda k: WD.tick(solver, d, st, k=k, first=(k == 0), **WALK), WD.terrain_swap(d),
+                      dict(mask=st["mask"], events=d["events"], contact=st["contact"], status=d["tick"]["status"], phase=st["phase"]))
     # the word after the last step, as the next tick's gait_estimated would form it
-    solver.contact_estimate(d["mats"]["Jc"], st["r"], st["f" + str((ticks - 1) % 2)], d["normals"], st["contact"])
+    solver.contact_estimate(d["tick"]["Jc"], st["r"], st["f" + str((ticks - 1) % 2)], d["normals"], st["contact"])
     torch.cuda.synchronize()
-    rec = {k: x.cpu().numpy() for k, x in rec.items()}
     assert np.all(rec["status"] == 0)
     assert np.array_equal(rec["mask"], cpu["masks"]) and np.array_equal(rec["events"], cpu["events"])
     assert np.all(rec["contact"][0] == 0) and np.array_equal(rec["contact"][1:], cpu["contacts"][:-1])
     assert np.array_equal(st["contact"].cpu().numpy(), cpu["contacts"][-1])
-    early = GND.early_touchdowns(GR.walk_params(flat_model), phases.cpu().numpy(), rec["events"])
+    early = GND.early_touchdowns(GR.walk_params(flat_model), rec["phase"], rec["events"])
     assert early == cpu["early"]
     eq, ev = relerr(to_host(st["q"]), cpu["q"]), relerr(to_host(st["v"]), cpu["v"])
     print("estimated walking loop: q %.3g v %.3g (gate %.3g); %d early touchdowns" % (eq, ev, gate, len(early)))

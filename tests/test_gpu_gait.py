@@ -11,9 +11,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests import gait_ref as GR, limit_models, swing_ref as SR
-from tests.util import elementwise_excess, relerr, to_dev, to_host
-from wbc_quadruped_dob_amd import synth
+from tests import gait_ref as GR, limit_models, walk_dev as WD
+from tests.util import gate as parity_gate, relerr, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 SIZES = GR.PARITY_SIZES
@@ -28,23 +27,7 @@ def torch_cuda():
     return torch
 
 
-def _solver(model, dtype="f64", max_batch=64, dt=None, ref_params=None, gait=None, swing=None):
-    import wbc_quadruped_dob_amd as W
-    P = synth.default_params(observer_order=0, dtype=dtype)
-    if dt is not None:
-        P["dt"] = dt
-    s = W.Solver(model, W.Params.from_dict(P, dtype), dtype=dtype, device=0, max_batch=max_batch)
-    if ref_params is not None:
-        s.set_ref_params(ref_params)
-    if gait is not None:
-        s.set_gait_params(_gait_dict(gait))
-    if swing is not None:
-        s.set_swing_params(swing)
-    return s
-
-
-def _gait_dict(P):
-    return {k: (np.asarray(v) if k in ("duty", "offset", "base_xy") else v) for k, v in P.items()}
+_solver = WD.solver
 
 
 _FLATS = {}
@@ -76,12 +59,8 @@ def _dev_case(torch, c, dtype):
 
 
 def _gate(got, ref, dtype, what, n):
-    if ref.size == 0:
-        return
-    ex = elementwise_excess(got, ref) if dtype == "f64" else elementwise_excess(got, ref, rtol=0.0, atol_frac=F32_GATE[what])
-    print("%s %s n=%d: excess %.3g (max |ref| %.3g, max |diff| %.3g)" % (what, dtype, n, ex, np.abs(ref).max(), np.abs(np.asarray(got, np.float64) - ref).max()))
-    assert np.all(np.isfinite(got)), what
-    assert ex <= 1.0, (what, ex)
+    if ref.size:
+        parity_gate(got, ref, dtype, what, n, F32_GATE)
 
 
 def _check_parity(got, c, ref, dtype, n, retarget=1):
@@ -255,73 +234,27 @@ def test_single_robot_call_equals_the_batch_call(torch_cuda, gpu_model, flat_mod
         assert np.array_equal(sw, got["swing"][s]), s
 
 
-# ---- the four-call tick: gait -> reference_swing -> step -> integrate
-def _walk_solver(model, flat, n):
-    return _solver(model, "f64", max_batch=n, dt=GR.DYADIC_DT, ref_params=SR.loop_ref_params(), gait=GR.walk_params(flat), swing=GR.WALK_SWING_PARAMS)
-
-
-def _walk_dev(torch, case):
-    td = torch.float64
-    d = {k: to_dev(case[k], torch, td) for k in ("cmd", "plan", "normals", "mu")}
-    n = case["q"].shape[0]
-    e = lambda r: torch.zeros((r, n), dtype=td, device="cuda")
-    i = lambda: torch.zeros(n, dtype=torch.int32, device="cuda")
-    d["ref"] = dict(w_des=e(6), vdot_des=e(18), foot=e(24))
-    d["tick"] = dict(tau=e(12), f=e(12), status=i(), iters=i(), M=e(171), h=e(18), Jc=e(216), pf=e(12))
-    d["events"] = i()
-    return d
-
-
-def _walk_state(torch, case):
-    td = torch.float64
-    return dict(q=to_dev(case["q"], torch, td), v=to_dev(case["v"], torch, td), phase=torch.from_numpy(case["phase"]).to(td).cuda(),
-                mask=torch.from_numpy(case["mask"]).to(torch.int32).cuda(), swing=to_dev(case["swing"], torch, td))
-
-
-def _tick(solver, d, st):
-    """One walking tick on the state st (q, v, phase, mask, swing advance in place).  reference_swing has ONE t for the CoM plan and the swing law, and
-    the swing law must get 0 (the gait call wrote t0): the CoM plan's clock travels in the plan's elapsed-time word, row 7"""
-    solver.gait(st["q"], st["v"], d["cmd"], st["phase"], st["mask"], st["swing"], events=d["events"])
-    solver.reference_swing(st["q"], st["v"], d["plan"], st["mask"], st["swing"], 0.0, out=d["ref"], want_foot=True)
-    solver.step(st["q"], st["v"], d["ref"]["w_des"], d["ref"]["vdot_des"], d["normals"], d["mu"], st["mask"], out=d["tick"], want_mats=True)
-    solver.integrate(st["q"], st["v"], d["tick"]["M"], d["tick"]["h"], d["tick"]["Jc"], d["tick"]["tau"], d["tick"]["f"])
-
-
+# ---- the four-call tick: gait -> reference_swing -> step -> integrate (walk_dev.tick on the rigid plant, nothing sensed)
 def test_captured_four_call_tick_replays_bit_for_bit(torch_cuda, gpu_model, flat_model, oracle):
     """gait -> reference_swing -> step -> integrate at N = 17, captured once: three replays from the same start = three eager ticks, bit for bit,
     and the first of them lifts two feet off (phase 0, all feet down: feet 1 and 2 are 1/128 into their swing window)."""
     torch = torch_cuda
     n = 17
     case = GR.walk_case(flat_model, oracle, n)
-    solver = _walk_solver(gpu_model, flat_model, n)
-    d = _walk_dev(torch, case)
-    start = _walk_state(torch, case)
+    solver = WD.walk_solver(gpu_model, flat_model, n)
+    d = WD.buffers(torch, case, foot=True)
+    start = WD.state(torch, case)
     st = {k: x.clone() for k, x in start.items()}
     lifted = []
     for _ in range(3):
-        _tick(solver, d, st)
+        WD.tick(solver, d, st)
         lifted.append(d["events"].clone())
     torch.cuda.synchronize()
     assert torch.all(lifted[0] == 0b0110) and torch.all(st["mask"] == 0b1001)
     eager = {k: x.clone() for k, x in st.items()}
     eager["tau"] = d["tick"]["tau"].clone()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):   # warm-up on the side stream (torch's capture recipe)
-        _tick(solver, d, {k: x.clone() for k, x in start.items()})
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    for k in st:
-        st[k].copy_(start[k])
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        _tick(solver, d, st)
-    solver.set_gait_params(dict(period=1.0, duty=1.0))   # a captured graph keeps the schedule it was captured with
-    for k in st:
-        st[k].copy_(start[k])
-    for _ in range(3):
-        g.replay()
-    torch.cuda.synchronize()
+    WD.capture_replay(torch, lambda: WD.tick(solver, d, st), WD.rewinder(st, start), 3,
+                      lambda: solver.set_gait_params(dict(period=1.0, duty=1.0)))   # a captured graph keeps the schedule it was captured with
     for k in st:
         assert torch.equal(st[k], eager[k]), k
     assert torch.equal(d["tick"]["tau"], eager["tau"])
@@ -336,24 +269,15 @@ def test_closed_loop_matches_the_cpu_loop_and_lands(torch_cuda, gpu_model, flat_
     n, ticks = 16, GR.WALK_TICKS
     case, cpu = GR.cpu_walk(flat_model, oracle, n)
     assert cpu["status_ok"]
-    solver = _walk_solver(gpu_model, flat_model, n)
-    d = _walk_dev(torch, case)
-    st = _walk_state(torch, case)
-    td = torch.float64
-    masks = torch.zeros((ticks, n), dtype=torch.int32, device="cuda")
-    events = torch.zeros((ticks, n), dtype=torch.int32, device="cuda")
-    status = torch.zeros((ticks, n), dtype=torch.int32, device="cuda")
-    feet = torch.zeros((ticks, 24, n), dtype=td, device="cuda")
-    swings = torch.zeros((ticks, 36, n), dtype=td, device="cuda")
-    for k in range(ticks):
-        d["plan"][7] = k * GR.DYADIC_DT                   # the CoM plan's elapsed time (a fill on the stream, no synchronisation)
-        _tick(solver, d, st)
-        masks[k].copy_(st["mask"]); events[k].copy_(d["events"]); status[k].copy_(d["tick"]["status"])
-        feet[k].copy_(d["ref"]["foot"]); swings[k].copy_(st["swing"])
+    solver = WD.walk_solver(gpu_model, flat_model, n)
+    d = WD.buffers(torch, case, foot=True)
+    st = WD.state(torch, case)
+    rec = WD.run_loop(torch, d, ticks, lambda k: WD.tick(solver, d, st),
+                      record=dict(masks=st["mask"], events=d["events"], status=d["tick"]["status"], feet=d["ref"]["foot"], swings=st["swing"]))
     foot = solver.swing_reference(st["q"], st["v"], st["mask"], st["swing"], 0.0, vdot_des=d["ref"]["vdot_des"], want_foot=True)["foot"]
     torch.cuda.synchronize()
-    masks, events, feet, swings = masks.cpu().numpy(), events.cpu().numpy(), feet.cpu().numpy(), swings.cpu().numpy()
-    assert np.all(status.cpu().numpy() == 0)
+    masks, events, feet, swings = (rec[k] for k in ("masks", "events", "feet", "swings"))
+    assert np.all(rec["status"] == 0)
     assert np.array_equal(masks, cpu["masks"]) and np.array_equal(events, cpu["events"])
     q, v, foot = to_host(st["q"]), to_host(st["v"]), to_host(foot)
     pos = lambda f: f.reshape(n, 4, 6)[:, :, :3]

@@ -14,8 +14,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests import gait_ref as GR, ground_ref as R, limit_models, limit_ref, swing_ref as SR
-from tests.util import elementwise_excess, relerr, to_dev, to_host
+from tests import gait_ref as GR, ground_ref as R, limit_models, limit_ref, swing_ref as SR, walk_dev as WD
+from tests.util import gate as parity_gate, relerr, to_dev, to_host, torch_dtype as _td
 from wbc_quadruped_dob_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -33,21 +33,8 @@ def torch_cuda():
     return torch
 
 
-def _solver(model, dtype="f64", max_batch=64, dt=None, ground=None, ref_params=None, gait=None, swing=None):
-    import wbc_quadruped_dob_amd as W
-    P = synth.default_params(observer_order=0, dtype=dtype)
-    if dt is not None:
-        P["dt"] = dt
-    s = W.Solver(model, W.Params.from_dict(P, dtype), dtype=dtype, device=0, max_batch=max_batch)
-    if ground is not None:
-        s.set_ground_params(ground)
-    if ref_params is not None:
-        s.set_ref_params(ref_params)
-    if gait is not None:
-        s.set_gait_params({k: (np.asarray(v) if k in ("duty", "offset", "base_xy") else v) for k, v in gait.items()})
-    if swing is not None:
-        s.set_swing_params(swing)
-    return s
+_solver = WD.solver
+_gate = functools.partial(parity_gate, f32_gate=F32_GATE)
 
 
 _FLATS = {}
@@ -66,10 +53,6 @@ def _case(flat_id, n):
     ref = R.integrate_ground(R.params(), DT, c["dyn"], c["tau"], c["normals"], c["height"], c["mu"], c["tau_ext"], c["q"], c["v"],
                              limit_ref.leg_joints(flat))
     return c, ref
-
-
-def _td(torch, dtype):
-    return torch.float64 if dtype == "f64" else torch.float32
 
 
 def _dev_case(torch, c, dtype):
@@ -97,13 +80,6 @@ def _plant(torch, solver, d, o, q, v):
                             contact=o["contact"], gap=o["gap"])
     torch.cuda.synchronize()
     return dict(f_gr=to_host(o["f_gr"]), contact=o["contact"].cpu().numpy(), gap=to_host(o["gap"]), q=to_host(q), v=to_host(v))
-
-
-def _gate(got, ref, dtype, what, n):
-    ex = elementwise_excess(got, ref) if dtype == "f64" else elementwise_excess(got, ref, rtol=0.0, atol_frac=F32_GATE[what])
-    print("%s %s n=%d: excess %.3g (max |ref| %.3g, max |diff| %.3g)" % (what, dtype, n, ex, np.abs(ref).max(), np.abs(np.asarray(got, np.float64) - ref).max()))
-    assert np.all(np.isfinite(got)), what
-    assert ex <= 1.0, (what, ex)
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -311,37 +287,8 @@ def test_set_ground_params_reaches_the_kernel(torch_cuda, gpu_model, dtype):
     assert np.all(a["contact"].cpu().numpy() == 15) and np.all(b["contact"].cpu().numpy() == 0)      # 80 N > 5 N; 160 N < 200 N
 
 
-# ---- the four-call tick: gait(contact = last tick's) -> reference_swing -> step -> integrate_ground
-def _walk_solver(model, flat, n):
-    return _solver(model, "f64", max_batch=n, dt=GR.DYADIC_DT, ref_params=SR.loop_ref_params(), gait=GR.walk_params(flat), swing=GR.WALK_SWING_PARAMS)
-
-
-def _walk_dev(torch, case):
-    td = torch.float64
-    d = {k: to_dev(case[k], torch, td) for k in ("cmd", "plan", "normals", "mu", "height0", "height1")}
-    n = case["q"].shape[0]
-    e = lambda r: torch.zeros((r, n), dtype=td, device="cuda")
-    i = lambda: torch.zeros(n, dtype=torch.int32, device="cuda")
-    d["ref"] = dict(w_des=e(6), vdot_des=e(18))
-    d["tick"] = dict(tau=e(12), f=e(12), status=i(), iters=i(), M=e(171), h=e(18), Jc=e(216), pf=e(12))
-    d["events"], d["f_gr"], d["height"] = i(), e(12), d["height0"].clone()
-    return d
-
-
-def _walk_state(torch, case):
-    td = torch.float64
-    return dict(q=to_dev(case["q"], torch, td), v=to_dev(case["v"], torch, td), phase=torch.from_numpy(case["phase"]).to(td).cuda(),
-                mask=torch.from_numpy(case["mask"]).to(torch.int32).cuda(), swing=to_dev(case["swing"], torch, td),
-                contact=torch.zeros(case["q"].shape[0], dtype=torch.int32, device="cuda"))
-
-
-def _tick(solver, d, st):
-    """One walking tick on the state st (q, v, phase, mask, swing, contact advance in place); no host work between the four launches"""
-    solver.gait(st["q"], st["v"], d["cmd"], st["phase"], st["mask"], st["swing"], contact=st["contact"], events=d["events"])
-    solver.reference_swing(st["q"], st["v"], d["plan"], st["mask"], st["swing"], 0.0, out=d["ref"])
-    solver.step(st["q"], st["v"], d["ref"]["w_des"], d["ref"]["vdot_des"], d["normals"], d["mu"], st["mask"], out=d["tick"], want_mats=True)
-    solver.integrate_ground(st["q"], st["v"], d["tick"]["M"], d["tick"]["h"], d["tick"]["Jc"], d["tick"]["tau"], d["normals"], d["height"], d["mu"],
-                            f_gr=d["f_gr"], contact=st["contact"])
+# ---- the four-call tick: gait(contact = last tick's) -> reference_swing -> step -> integrate_ground (walk_dev.tick)
+WALK = dict(plant="ground", sense="plant")
 
 
 def test_captured_four_call_tick_replays_bit_for_bit(torch_cuda, gpu_model, flat_model, oracle):
@@ -350,34 +297,19 @@ def test_captured_four_call_tick_replays_bit_for_bit(torch_cuda, gpu_model, flat
     torch = torch_cuda
     n = 17
     case = R.walk_case(flat_model, oracle, n)
-    solver = _walk_solver(gpu_model, flat_model, n)
-    d = _walk_dev(torch, case)
+    solver = WD.walk_solver(gpu_model, flat_model, n)
+    d = WD.buffers(torch, case, "ground")
     d["height"] += 1e-3
-    start = _walk_state(torch, case)
+    start = WD.state(torch, case, "ground")
     st = {k: x.clone() for k, x in start.items()}
     for _ in range(3):
-        _tick(solver, d, st)
+        WD.tick(solver, d, st, **WALK)
     torch.cuda.synchronize()
     assert torch.all(st["mask"] == 0b1001) and bool((st["contact"] != 0).all())
     eager = {k: x.clone() for k, x in st.items()}
     eager["f_gr"] = d["f_gr"].clone()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):   # warm-up on the side stream (torch's capture recipe)
-        _tick(solver, d, {k: x.clone() for k, x in start.items()})
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    for k in st:
-        st[k].copy_(start[k])
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        _tick(solver, d, st)
-    solver.set_ground_params(dict(k_n=1.0, c_n=0.0, c_t=0.0))   # a captured graph keeps the law it was captured with
-    for k in st:
-        st[k].copy_(start[k])
-    for _ in range(3):
-        g.replay()
-    torch.cuda.synchronize()
+    WD.capture_replay(torch, lambda: WD.tick(solver, d, st, **WALK), WD.rewinder(st, start), 3,
+                      lambda: solver.set_ground_params(dict(k_n=1.0, c_n=0.0, c_t=0.0)))   # a captured graph keeps the law it was captured with
     for k in st:
         assert torch.equal(st[k], eager[k]), k
     assert torch.equal(d["f_gr"], eager["f_gr"]) and bool((d["f_gr"] != 0).any())
@@ -395,23 +327,14 @@ def test_closed_loop_matches_the_cpu_loop(torch_cuda, gpu_model, flat_model, ora
     assert cpu["status_ok"] and len(cpu["early"]) >= 1
     gate = max(1e-6, 10 * R.WALK_AMPLIFICATION * 1e-9)
     assert gate <= 1e-3
-    solver = _walk_solver(gpu_model, flat_model, n)
-    d = _walk_dev(torch, case)
-    st = _walk_state(torch, case)
-    rec = {k: torch.zeros((ticks, n), dtype=torch.int32, device="cuda") for k in ("mask", "events", "contact", "status")}
-    phases = torch.zeros((ticks, n), dtype=torch.float64, device="cuda")
-    for k in range(ticks):
-        d["plan"][7] = k * GR.DYADIC_DT                   # the CoM plan's elapsed time (a fill on the stream, no synchronisation)
-        if k == R.BUMP_TICK:
-            d["height"].copy_(d["height1"])
-        _tick(solver, d, st)
-        rec["mask"][k].copy_(st["mask"]); rec["events"][k].copy_(d["events"]); rec["contact"][k].copy_(st["contact"])
-        rec["status"][k].copy_(d["tick"]["status"]); phases[k].copy_(st["phase"])
-    torch.cuda.synchronize()
-    rec = {k: x.cpu().numpy() for k, x in rec.items()}
+    solver = WD.walk_solver(gpu_model, flat_model, n)
+    d = WD.buffers(torch, case, "ground")
+    st = WD.state(torch, case, "ground")
+    rec = WD.run_loop(torch, d, ticks, lambda k: WD.tick(solver, d, st, **WALK), WD.terrain_swap(d),
+                      dict(mask=st["mask"], events=d["events"], contact=st["contact"], status=d["tick"]["status"], phase=st["phase"]))
     assert np.all(rec["status"] == 0)
     assert np.array_equal(rec["mask"], cpu["masks"]) and np.array_equal(rec["events"], cpu["events"]) and np.array_equal(rec["contact"], cpu["contacts"])
-    early = R.early_touchdowns(GR.walk_params(flat_model), phases.cpu().numpy(), rec["events"])
+    early = R.early_touchdowns(GR.walk_params(flat_model), rec["phase"], rec["events"])
     assert early == cpu["early"]
     eq, ev = relerr(to_host(st["q"]), cpu["q"]), relerr(to_host(st["v"]), cpu["v"])
     print("walking loop on the ground plant: q %.3g v %.3g (gate %.3g); %d early touchdowns" % (eq, ev, gate, len(early)))

@@ -15,8 +15,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests import gait_ref as GR, ground_ref as R, limit_models, limit_ref, stick_ref as S, swing_ref as SR
-from tests.util import elementwise_excess, relerr, to_dev, to_host
+from tests import ground_ref as R, limit_models, limit_ref, stick_ref as S, swing_ref as SR, walk_dev as WD
+from tests.util import gate as parity_gate, relerr, to_dev, to_host, torch_dtype as _td
 from wbc_quadruped_dob_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -34,23 +34,8 @@ def torch_cuda():
     return torch
 
 
-def _solver(model, dtype="f64", max_batch=64, dt=None, ground=None, k_t=None, ref_params=None, gait=None, swing=None):
-    import wbc_quadruped_dob_amd as W
-    P = synth.default_params(observer_order=0, dtype=dtype)
-    if dt is not None:
-        P["dt"] = dt
-    s = W.Solver(model, W.Params.from_dict(P, dtype), dtype=dtype, device=0, max_batch=max_batch)
-    if ground is not None:
-        s.set_ground_params(ground)
-    if k_t is not None:
-        s.set_stiction_params(dict(k_t=k_t))
-    if ref_params is not None:
-        s.set_ref_params(ref_params)
-    if gait is not None:
-        s.set_gait_params({k: (np.asarray(v) if k in ("duty", "offset", "base_xy") else v) for k, v in gait.items()})
-    if swing is not None:
-        s.set_swing_params(swing)
-    return s
+_solver = WD.solver
+_gate = functools.partial(parity_gate, f32_gate=F32_GATE)
 
 
 _FLATS = {}
@@ -69,10 +54,6 @@ def _case(flat_id, n):
     ref = S.integrate_ground_stick(R.params(), S.DEFAULT_KT, DT, c["dyn"], c["tau"], c["normals"], c["height"], c["mu"], c["tau_ext"], c["q"], c["v"],
                                    c["anchor"], c["stick"], limit_ref.leg_joints(flat))
     return c, ref
-
-
-def _td(torch, dtype):
-    return torch.float64 if dtype == "f64" else torch.float32
 
 
 def _dev_case(torch, c, dtype):
@@ -107,13 +88,6 @@ def _plant(torch, solver, d, o):
     torch.cuda.synchronize()
     return dict(f_gr=to_host(o["f_gr"]), contact=o["contact"].cpu().numpy(), gap=to_host(o["gap"]), anchor=to_host(anchor), stick=stick.cpu().numpy(),
                 q=to_host(q), v=to_host(v))
-
-
-def _gate(got, ref, dtype, what, n):
-    ex = elementwise_excess(got, ref) if dtype == "f64" else elementwise_excess(got, ref, rtol=0.0, atol_frac=F32_GATE[what])
-    print("%s %s n=%d: excess %.3g (max |ref| %.3g, max |diff| %.3g)" % (what, dtype, n, ex, np.abs(ref).max(), np.abs(np.asarray(got, np.float64) - ref).max()))
-    assert np.all(np.isfinite(got)), what
-    assert ex <= 1.0, (what, ex)
 
 
 def _gate_law(got, g, anchor_in, dtype, n):
@@ -397,39 +371,8 @@ def test_ragged_tail_writes_nothing_beyond_the_batch(torch_cuda, gpu_model, flat
     assert td == d["q"].dtype
 
 
-# ---- the four-call tick: gait(contact = last tick's) -> reference_swing -> step -> integrate_ground_stick
-def _walk_solver(model, flat, n):
-    return _solver(model, "f64", max_batch=n, dt=GR.DYADIC_DT, ref_params=SR.loop_ref_params(), gait=GR.walk_params(flat), swing=GR.WALK_SWING_PARAMS)
-
-
-def _walk_dev(torch, case):
-    td = torch.float64
-    d = {k: to_dev(case[k], torch, td) for k in ("cmd", "plan", "normals", "mu", "height0", "height1")}
-    n = case["q"].shape[0]
-    e = lambda r: torch.zeros((r, n), dtype=td, device="cuda")
-    i = lambda: torch.zeros(n, dtype=torch.int32, device="cuda")
-    d["ref"] = dict(w_des=e(6), vdot_des=e(18))
-    d["tick"] = dict(tau=e(12), f=e(12), status=i(), iters=i(), M=e(171), h=e(18), Jc=e(216), pf=e(12))
-    d["events"], d["f_gr"], d["height"] = i(), e(12), d["height0"].clone()
-    return d
-
-
-def _walk_state(torch, case):
-    td = torch.float64
-    n = case["q"].shape[0]
-    return dict(q=to_dev(case["q"], torch, td), v=to_dev(case["v"], torch, td), phase=torch.from_numpy(case["phase"]).to(td).cuda(),
-                mask=torch.from_numpy(case["mask"]).to(torch.int32).cuda(), swing=to_dev(case["swing"], torch, td),
-                contact=torch.zeros(n, dtype=torch.int32, device="cuda"), anchor=torch.zeros((12, n), dtype=td, device="cuda"),
-                stick=torch.zeros(n, dtype=torch.int32, device="cuda"))       # the caller stores 0 into stick before the first tick
-
-
-def _tick(solver, d, st):
-    """One walking tick on the state st (q, v, phase, mask, swing, contact, anchor, stick advance in place); no host work between the four launches"""
-    solver.gait(st["q"], st["v"], d["cmd"], st["phase"], st["mask"], st["swing"], contact=st["contact"], events=d["events"])
-    solver.reference_swing(st["q"], st["v"], d["plan"], st["mask"], st["swing"], 0.0, out=d["ref"])
-    solver.step(st["q"], st["v"], d["ref"]["w_des"], d["ref"]["vdot_des"], d["normals"], d["mu"], st["mask"], out=d["tick"], want_mats=True)
-    solver.integrate_ground_stick(st["q"], st["v"], d["tick"]["M"], d["tick"]["h"], d["tick"]["Jc"], d["tick"]["tau"], d["normals"], d["height"],
-                                  d["mu"], st["anchor"], st["stick"], f_gr=d["f_gr"], contact=st["contact"])
+# ---- the four-call tick: gait(contact = last tick's) -> reference_swing -> step -> integrate_ground_stick (walk_dev.tick)
+WALK = dict(plant="stick", sense="plant")
 
 
 def test_captured_four_call_tick_replays_bit_for_bit(torch_cuda, gpu_model, flat_model, oracle):
@@ -438,33 +381,18 @@ def test_captured_four_call_tick_replays_bit_for_bit(torch_cuda, gpu_model, flat
     torch = torch_cuda
     n = 17
     case = S.walk_case(flat_model, oracle, n)
-    solver = _walk_solver(gpu_model, flat_model, n)
-    d = _walk_dev(torch, case)
-    start = _walk_state(torch, case)
+    solver = WD.walk_solver(gpu_model, flat_model, n)
+    d = WD.buffers(torch, case, "stick")
+    start = WD.state(torch, case, "stick")
     st = {k: x.clone() for k, x in start.items()}
     for _ in range(3):
-        _tick(solver, d, st)
+        WD.tick(solver, d, st, **WALK)
     torch.cuda.synchronize()
     assert bool((st["contact"] != 0).all()) and bool(((st["stick"] & 0xf) != 0).all()) and bool((st["anchor"] != 0).any())
     eager = {k: x.clone() for k, x in st.items()}
     eager["f_gr"] = d["f_gr"].clone()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):   # warm-up on the side stream (torch's capture recipe)
-        _tick(solver, d, {k: x.clone() for k, x in start.items()})
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    for k in st:
-        st[k].copy_(start[k])
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        _tick(solver, d, st)
-    solver.set_stiction_params(dict(k_t=1.0))   # a captured graph keeps the law it was captured with
-    for k in st:
-        st[k].copy_(start[k])
-    for _ in range(3):
-        g.replay()
-    torch.cuda.synchronize()
+    WD.capture_replay(torch, lambda: WD.tick(solver, d, st, **WALK), WD.rewinder(st, start), 3,
+                      lambda: solver.set_stiction_params(dict(k_t=1.0)))   # a captured graph keeps the law it was captured with
     for k in st:
         assert torch.equal(st[k], eager[k]), k
     assert torch.equal(d["f_gr"], eager["f_gr"]) and bool((d["f_gr"] != 0).any())
@@ -481,19 +409,11 @@ def test_closed_loop_matches_the_cpu_loop(torch_cuda, gpu_model, flat_model, ora
     assert cpu["status_ok"] and len(cpu["early"]) >= 1
     gate = max(1e-6, 10 * S.WALK_AMPLIFICATION * 1e-9)
     assert gate <= 1e-3
-    solver = _walk_solver(gpu_model, flat_model, n)
-    d = _walk_dev(torch, case)
-    st = _walk_state(torch, case)
-    rec = {k: torch.zeros((ticks, n), dtype=torch.int32, device="cuda") for k in ("mask", "events", "contact", "stick", "status")}
-    for k in range(ticks):
-        d["plan"][7] = k * GR.DYADIC_DT                   # the CoM plan's elapsed time (a fill on the stream, no synchronisation)
-        if k == R.BUMP_TICK:
-            d["height"].copy_(d["height1"])
-        _tick(solver, d, st)
-        rec["mask"][k].copy_(st["mask"]); rec["events"][k].copy_(d["events"]); rec["contact"][k].copy_(st["contact"])
-        rec["stick"][k].copy_(st["stick"]); rec["status"][k].copy_(d["tick"]["status"])
-    torch.cuda.synchronize()
-    rec = {k: x.cpu().numpy() for k, x in rec.items()}
+    solver = WD.walk_solver(gpu_model, flat_model, n)
+    d = WD.buffers(torch, case, "stick")
+    st = WD.state(torch, case, "stick")
+    rec = WD.run_loop(torch, d, ticks, lambda k: WD.tick(solver, d, st, **WALK), WD.terrain_swap(d),
+                      dict(mask=st["mask"], events=d["events"], contact=st["contact"], stick=st["stick"], status=d["tick"]["status"]))
     assert np.all(rec["status"] == 0)
     assert np.array_equal(rec["mask"], cpu["masks"]) and np.array_equal(rec["events"], cpu["events"])
     assert np.array_equal(rec["contact"], cpu["contacts"]) and np.array_equal(rec["stick"], cpu["sticks"])
@@ -510,27 +430,23 @@ def test_slope_hold(torch_cuda, gpu_model, flat_model, oracle):
     n, ticks = 16, S.SLOPE_TICKS
     case, vis = S.cpu_slope(flat_model, oracle, 0.0)
     viscous = float(np.linalg.norm(S.drift(vis)[0]))
-    td = torch.float64
-    rep = lambda a: to_dev(np.repeat(a, n, 0), torch, td)
+    padded = {k: np.repeat(case[k], n, 0) for k in ("q", "v", "plan", "normals", "height", "mu", "mask", "swing")}
     solver = _solver(gpu_model, "f64", max_batch=n, ref_params=SR.loop_ref_params())
-    q, v, plan, normals, height, mu = (rep(case[k]) for k in ("q", "v", "plan", "normals", "height", "mu"))
-    mask = torch.full((n,), 0b1111, dtype=torch.int32, device="cuda")
-    e = lambda r: torch.zeros((r, n), dtype=td, device="cuda")
-    i = lambda: torch.zeros(n, dtype=torch.int32, device="cuda")
-    ref = dict(w_des=e(6), vdot_des=e(18))
-    tick = dict(tau=e(12), f=e(12), status=i(), iters=i(), M=e(171), h=e(18), Jc=e(216), pf=e(12))
-    anchor, stick, f_gr = e(12), i(), e(12)
+    d = WD.buffers(torch, padded, "stick")
+    st = WD.state(torch, padded, "stick")
+    ref, tick, q, v = d["ref"], d["tick"], st["q"], st["v"]
+    assert bool((st["mask"] == 0b1111).all())
     sticks = torch.zeros((ticks, n), dtype=torch.int32, device="cuda")
     status = torch.zeros((ticks, n), dtype=torch.int32, device="cuda")
     pf_from = None
     for k in range(ticks):
-        solver.reference(q, v, plan, 0.0, out=ref)
-        solver.step(q, v, ref["w_des"], ref["vdot_des"], normals, mu, mask, out=tick, want_mats=True)
+        solver.reference(q, v, d["plan"], 0.0, out=ref)
+        solver.step(q, v, ref["w_des"], ref["vdot_des"], d["normals"], d["mu"], st["mask"], out=tick, want_mats=True)
         if k == S.SLOPE_FROM:
             pf_from = tick["pf"].clone()
-        solver.integrate_ground_stick(q, v, tick["M"], tick["h"], tick["Jc"], tick["tau"], normals, height, mu, anchor, stick, f_gr=f_gr,
-                                      want_contact=False)
-        sticks[k].copy_(stick); status[k].copy_(tick["status"])
+        solver.integrate_ground_stick(q, v, tick["M"], tick["h"], tick["Jc"], tick["tau"], d["normals"], d["height"], d["mu"], st["anchor"], st["stick"],
+                                      f_gr=d["f_gr"], want_contact=False)
+        sticks[k].copy_(st["stick"]); status[k].copy_(tick["status"])
     torch.cuda.synchronize()
     mean = lambda t: to_host(t).reshape(n, 4, 3).mean(1)
     moved = np.linalg.norm(mean(tick["pf"]) - mean(pf_from), axis=1)

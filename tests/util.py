@@ -29,6 +29,18 @@ def elementwise_excess(a, b, rtol=1e-6, atol_frac=1e-9):
     return float(np.max(np.abs(a - b) / np.maximum(bound, np.finfo(np.float64).tiny)))
 
 
+def torch_dtype(torch, dtype):
+    return torch.float64 if dtype == "f64" else torch.float32
+
+
+def gate(got, ref, dtype, what, n, f32_gate):
+    """The gate of the GPU parity tests: fp64 at elementwise_excess' standing tolerances, fp32 at f32_gate[what] of the largest entry"""
+    ex = elementwise_excess(got, ref) if dtype == "f64" else elementwise_excess(got, ref, rtol=0.0, atol_frac=f32_gate[what])
+    print("%s %s n=%d: excess %.3g (max |ref| %.3g, max |diff| %.3g)" % (what, dtype, n, ex, np.abs(ref).max(), np.abs(np.asarray(got, np.float64) - ref).max()))
+    assert np.all(np.isfinite(got)), what
+    assert ex <= 1.0, (what, ex)
+
+
 def to_dev(x, torch, dtype):
     """row-per-state numpy [N, c] -> component-major device tensor [c, N]"""
     t = torch.from_numpy(np.ascontiguousarray(np.asarray(x).T))
