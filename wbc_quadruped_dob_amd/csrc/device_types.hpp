@@ -110,7 +110,7 @@ template <class T> struct SweepArgs {
 // [row][16 slots], in LDS for the whole launch.  The integrator writes the new state there (and to memory); the roles of the next tick read it from
 // there instead of waiting for those stores and a trip through L2 at the head of the tick.
 constexpr int SIMG_V = 19, SIMG_WORDS = 37;
-// The result image of a rollout workgroup (QpSync::res, qp_group16.hip.hpp): this tick's tau (rows 0 .. 11, caller's joint order), f (12 .. 23), h (24 .. 41),
+// The result image of a rollout workgroup (QpSync::res, qp_row16.hip.hpp): this tick's tau (rows 0 .. 11, caller's joint order), f (12 .. 23), h (24 .. 41),
 // [row][16 slots]; rows 42 .. 59 hold the external torques of the workgroup's states for the whole launch.
 constexpr int RES_TAU = 0, RES_F = 12, RES_H = 24, RES_WORDS = 42;
 

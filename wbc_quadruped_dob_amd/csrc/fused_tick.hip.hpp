@@ -33,7 +33,7 @@ constexpr int FUSED_OBS_WAVES = 2;
 // QP's b waits for it), wave 7 the joint rows (rhat_joint -> LDS, counted on `ready`; needed in the torque map only).
 // The QP waves subtract rhat from b and tau_partial themselves.
 // MATS = false (the caller wants tau, f only): no mass_jac role, and the rnea role runs the single merged force chain.
-// Staged hand-over (QpSync, qp_group16.hip.hpp): the rnea role publishes the four lever arms right after its state
+// Staged hand-over (QpSync, qp_row16.hip.hpp): the rnea role publishes the four lever arms right after its state
 // loads and w_des right behind them (`gready` counts both) -- H and its factor need the former only, b the latter --
 // rhat follows from the observer role (`oready`,
 // first needed for g = -A^T S b) and tau_partial + the own-leg Jacobian blocks when the force recursions are done

@@ -1,4 +1,5 @@
-// qp_group16_kernel launches: GRF QP + torque map (units a7-a9; qp_group16.hip.hpp).
+// The stand-alone QP kernels' launches: GRF QP + torque map (units a7-a9; kernels in qp_kernels.hip.hpp and qp_lane.hip.hpp, bodies in qp_struct16.hip.hpp and,
+// for large fp32 tiles, qp_group16.hip.hpp).
 #include "k_common.hip.hpp"
 #include "qp_kernels.hip.hpp"
 #include "qp_lane.hip.hpp"

@@ -64,7 +64,9 @@ template <class T> hipError_t k_tile_tick(const LaunchCtx& L, bool observer, int
 // list (optional): solve the states list[4 .. 4 + list[0]) instead of the whole batch (qp_list_kernel; the count is reset by the
 // NEXT tick's front-half kernel, SweepArgs::qp_todo -- not here)
 // warm (tile = 0, no list): qp_group16_kernel<.., WARM>, every state starts from its active set in a.aset_in
-// body (tiles): 0 structured body on gathered inputs (qp_tile_kernel), 1 its lean fp32 form (from WBC_F32_DENSE_TILE_MIN states), 2 STAGED tiles --
+// tile = 0 runs the structured body (qp_struct16.hip.hpp) whatever the kernel's name says.
+// body (tiles): 0 structured body on gathered inputs (qp_tile_kernel), 1 the orthogonal-factor fp32 body instead (qp_group16.hip.hpp: fp32 only, tiles of
+// 64 ... 128 states, from WBC_F32_DENSE_TILE_MIN states on), 2 STAGED tiles --
 // qp_stile_kernel, the tile's inputs through LDS, twelve wavefronts per workgroup, tile <= STILE_MAX_TILE (a multiple of 4)
 template <class T> hipError_t k_qp(const LaunchCtx& L, bool rhat, int tile, const DevParams<T>& prm, const QpArgs<T>& a, const QpJidx& jmap,
                                   int* list = nullptr, bool warm = false, int body = 0);

@@ -91,7 +91,7 @@ __device__ __forceinline__ void limit_qp_state(const LimitArgs<T>& a, double* S,
   auto ld_ = [&](const T* p, size_t row) { return (double)p[row * N + s]; };
   double Acol[6] = {0, 0, 0, 0, 0, 0}, aj[3] = {0, 0, 0}, tau0 = 0;
   if (isvar) {
-    const double dx = ld_(a.Jc, (size_t)(3 * kv + 1) * 18 + 5), dy = ld_(a.Jc, (size_t)(3 * kv + 2) * 18 + 3), dz = ld_(a.Jc, (size_t)(3 * kv) * 18 + 4);
+    const double dx = ld_(a.Jc, JC_LEVER_WORD_((size_t), kv, 0)), dy = ld_(a.Jc, JC_LEVER_WORD_((size_t), kv, 1)), dz = ld_(a.Jc, JC_LEVER_WORD_((size_t), kv, 2));
     Acol[av] = 1;   // A = [1 ; [d]x] per foot: column av
     Acol[3] = av == 0 ? 0 : (av == 1 ? -dz : dy);
     Acol[4] = av == 0 ? dz : (av == 1 ? 0 : -dx);
@@ -99,7 +99,7 @@ __device__ __forceinline__ void limit_qp_state(const LimitArgs<T>& a, double* S,
     tau0 = ld_(a.tau, j);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      aj[c] = ld_(a.Jc, (size_t)(3 * kv + c) * 18 + 6 + j);
+      aj[c] = ld_(a.Jc, JC_LEG_WORD_((size_t), kv, c, j));
       tau0 += aj[c] * ld_(a.f, (size_t)(3 * kv + c));
     }
   }

@@ -3,7 +3,7 @@
 // wave per SIMD; without the observer passes the sweep runs at two.  Here the observer is a light kernel -- per leg only
 // the kinematics, body momenta, gravity terms and the own-leg Jacobian -- that runs in front of dyn_sweep<M, h, Jc + step>.
 // It reads q, v, tau_prev, f_prev and the observer state, writes the new state and rhat (18 words at WS_RHAT of the step
-// workspace); the QP kernel completes b = w_des - rhat_base and tau_partial - rhat_joint itself (qp_group16_body<.., RHAT>).
+// workspace); the QP kernel completes b = w_des - rhat_base and tau_partial - rhat_joint itself (RHAT of the QP bodies, qp_struct16.hip.hpp).
 // Round 1 measured this kernel at 236 us (N = 262 144, fp64: 255 VGPRs + a 324-byte spill), as long as the sweep it was
 // meant to relieve.  What held the registers was not the algorithm but two things the compiler did with it (found by a
 // liveness scan of the ISA, round 2): (1) the sweep's results only feed stores guarded by `live`, so the arithmetic was sunk

@@ -28,7 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "qp_general_args.hpp"
-#include "qp_group16.hip.hpp"   // dppx, gsum, KeyT (DPP helpers of the 16-lane solver)
+#include "qp_row16.hip.hpp"   // dppx, gsum, KeyT (DPP helpers of the 16-lane solvers)
 
 namespace wbc {
 
@@ -56,7 +56,7 @@ template <class T> __device__ __forceinline__ T qpg_wave_sum(T v) {
   return (qpg_rl(v, 0) + qpg_rl(v, 16)) + (qpg_rl(v, 32) + qpg_rl(v, 48));
 }
 // minimum and (one of) the lane(s) that hold it, the lowest on an exact tie; BIG = "no candidate".  Selection by the packed key of
-// qp_group16.hip.hpp (lane id in the low mantissa bits), the EXACT value of the winner is then read from its lane.
+// qp_row16.hip.hpp (lane id in the low mantissa bits), the EXACT value of the winner is then read from its lane.
 template <class T> __device__ __forceinline__ void qpg_wave_argmin(T& v, int& idx) {
   using K = KeyT<T>;
   T k = K::pack(v, idx);

@@ -1,10 +1,15 @@
 // The stand-alone GRF-QP kernels: one-wavefront workgroups (qp_group16_kernel), tiles dealt by predicted work -- inputs gathered per state (qp_tile_kernel) or
-// staged through LDS (qp_stile_kernel / qp_stile_body, round 6: also the second half of tile_tick_kernel) --, the dense solver over a device-side list (qp_list_kernel).  The per-QP body is qp_body (qp_struct16.hip.hpp): the structured
-// wrench-space form in fp64, the orthogonal-factor form (qp_group16.hip.hpp) in fp32.
+// staged through LDS (qp_stile_kernel / qp_stile_body, round 6: also the second half of tile_tick_kernel) --, the active-set solver over a device-side list (qp_list_kernel).
+// The per-QP body is qp_struct16_body (qp_struct16.hip.hpp), the structured wrench-space form in fp64 arithmetic, for both scalar types; large fp32 tiles
+// (qp_tile_kernel<float, .., DENSE>) alone run the orthogonal-factor form in fp32 arithmetic, qp_group16_body (qp_group16.hip.hpp).
+// (qp_group16_kernel keeps its name from the time it ran that body: kernel names are symbols of the library, and a rename moves every unit's device code.)
 #pragma once
 #include "qp_struct16.hip.hpp"
+#include "qp_group16.hip.hpp"
 
 namespace wbc {
+
+constexpr int WBC_QP_WAVES = 2;
 
 // RHAT: rhat comes from the separate observer kernel through the HBM workspace (large observer-on batches)
 // WARM: every state's iteration starts from the active set in a.aset_in (wbc_step_batch_warm: dependent ticks)
@@ -47,19 +52,21 @@ constexpr int QP_PRE_WORDS = 48;
 // A = the arithmetic type: the storage type T, except that a predictor that feeds the (fp64-arithmetic) solver works in double.
 template <class T, bool PRE> struct PredA { using type = typename std::conditional<PRE, double, T>::type; };
 template <class A> struct PredPart { int cnt; A mag; bool fin_ok; A zf0, zf1, zf2, zm0, zm1, zm2; };
+// the lever arm of foot f_ of the predictor's state: from Jc, or from the workspace (ticks without M, h, Jc)
+#define PLD_D(f_, dx_, dy_, dz_) do { \
+    if (a.Jc) { dx_ = GLD(a.Jc, JC_LEVER_WORD(f_, 0)); dy_ = GLD(a.Jc, JC_LEVER_WORD(f_, 1)); dz_ = GLD(a.Jc, JC_LEVER_WORD(f_, 2)); } \
+    else { dx_ = GLD(a.ws, WS_D + 3 * (f_)); dy_ = GLD(a.ws, WS_D + 3 * (f_) + 1); dz_ = GLD(a.ws, WS_D + 3 * (f_) + 2); } } while (0)
 template <class T, bool RHAT, bool PRE = false>
 WBC_DEV void qp_predict_part(const DevParams<T>& prm, const QpArgs<T>& a, unsigned s32, unsigned N32, double* pre, int fmask, int cmask,
                              PredPart<typename PredA<T, PRE>::type>& out) {
   using A = typename PredA<T, PRE>::type;
-#define PLD(ptr, comp) ((A)(*(const T*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T)))))
+  using RowS = T;
+  using RowA = A;
   constexpr bool FIN = (std::is_same<T, float>::value);
   const int mask = a.mask[s32] & 0xF;
   const A s0 = prm.sS[0], s1 = prm.sS[1], s2 = prm.sS[2], s3 = prm.sS[3], s4 = prm.sS[4], s5 = prm.sS[5];
   // (loops over the feet are NOT unrolled where they carry per-foot data: with Dx..Dz[4] and the four feet's normals in flight the
   //  predictor needed 220-250 VGPRs -- more than the solver it serves; the lever arms are re-read, L2-hot, where they are needed)
-#define PLD_D(f_, dx_, dy_, dz_) do { \
-    if (a.Jc) { dx_ = PLD(a.Jc, (3 * (f_) + 1) * 18 + 5); dy_ = PLD(a.Jc, (3 * (f_) + 2) * 18 + 3); dz_ = PLD(a.Jc, (3 * (f_)) * 18 + 4); } \
-    else { dx_ = PLD(a.ws, WS_D + 3 * (f_)); dy_ = PLD(a.ws, WS_D + 3 * (f_) + 1); dz_ = PLD(a.ws, WS_D + 3 * (f_) + 2); } } while (0)
   A nc = 0, sx = 0, sy = 0, sz = 0, Pxx = 0, Pxy = 0, Pxz = 0, Pyy = 0, Pyz = 0, Pzz = 0;
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
@@ -72,55 +79,23 @@ WBC_DEV void qp_predict_part(const DevParams<T>& prm, const QpArgs<T>& a, unsign
   }
   A bt[6];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) bt[k] = (a.wdes ? PLD(a.wdes, k) : PLD(a.ws, WS_B + k)) - (RHAT ? PLD(a.ws, WS_RHAT + k) : (A)0);
-  // G = alpha I + B B^A and its factor, as in qp_group16_body (selection only: seed-accuracy reciprocal square roots)
-  const A g00 = prm.alpha + s0 * s0 * nc, g11 = prm.alpha + s1 * s1 * nc, g22 = prm.alpha + s2 * s2 * nc;
-  const A gm01 = -(s3 * s1) * sz, gm02 = (s3 * s2) * sy, gm10 = (s4 * s0) * sz, gm12 = -(s4 * s2) * sx, gm20 = -(s5 * s0) * sy, gm21 = (s5 * s1) * sx;
-  const A m00 = prm.alpha + (s3 * s3) * (Pyy + Pzz), m11 = prm.alpha + (s4 * s4) * (Pxx + Pzz), m22 = prm.alpha + (s5 * s5) * (Pxx + Pyy);
-  const A m10 = -(s4 * s3) * Pxy, m20 = -(s5 * s3) * Pxz, m21 = -(s5 * s4) * Pyz;
+  for (int k = 0; k < 6; ++k) bt[k] = (a.wdes ? GLD(a.wdes, k) : GLD(a.ws, WS_B + k)) - (RHAT ? GLD(a.ws, WS_RHAT + k) : (A)0);
+  // G = alpha I + B B^T, its factor and z = G^-1 S^(1/2) b (qp_row16.hip.hpp; selection only: seed-accuracy reciprocal square roots)
   auto rs = [](A x) __attribute__((always_inline)) -> A {
     if constexpr (FIN || PRE) return rsqrt_nr(x);
     else if constexpr (std::is_same<A, double>::value) return __builtin_amdgcn_rsq(x); else return __builtin_amdgcn_rsqf(x);
   };
-  A il[6];
-  il[0] = rs(g00); il[1] = rs(g11); il[2] = rs(g22);
-  const A a01 = gm01 * il[1], a02 = gm02 * il[2], a10 = gm10 * il[0], a12 = gm12 * il[2], a20 = gm20 * il[0], a21 = gm21 * il[1];
-  const A c00 = m00 - a01 * a01 - a02 * a02, c11 = m11 - a10 * a10 - a12 * a12, c22 = m22 - a20 * a20 - a21 * a21;
-  const A c10 = m10 - a12 * a02, c20 = m20 - a21 * a01, c21 = m21 - a20 * a10;
-  il[3] = rs(c00);
-  const A b10 = c10 * il[3], b20 = c20 * il[3];
-  il[4] = rs(c11 - b10 * b10);
-  const A b21 = (c21 - b20 * b10) * il[4];
-  il[5] = rs(c22 - b20 * b20 - b21 * b21);
-  A w[6], z[6];   // z = G^-1 S^(1/2) b
-  w[0] = s0 * bt[0] * il[0]; w[1] = s1 * bt[1] * il[1]; w[2] = s2 * bt[2] * il[2];
-  w[3] = (s3 * bt[3] - a01 * w[1] - a02 * w[2]) * il[3];
-  w[4] = (s4 * bt[4] - a10 * w[0] - a12 * w[2] - b10 * w[3]) * il[4];
-  w[5] = (s5 * bt[5] - a20 * w[0] - a21 * w[1] - b20 * w[3] - b21 * w[4]) * il[5];
-  z[5] = w[5] * il[5];
-  z[4] = (w[4] - b21 * z[5]) * il[4];
-  z[3] = (w[3] - b10 * z[4] - b20 * z[5]) * il[3];
-  z[2] = (w[2] - a02 * z[3] - a12 * z[4]) * il[2];
-  z[1] = (w[1] - a01 * z[3] - a21 * z[5]) * il[1];
-  z[0] = (w[0] - a10 * z[4] - a20 * z[5]) * il[0];
+  WBC_QP_G_FACTOR(A, rs, prm.alpha)
+  A w[6], z[6];
+  WBC_QP_FWD(il, s0 * bt[0], s1 * bt[1], s2 * bt[2], s3 * bt[3], s4 * bt[4], s5 * bt[5], w);
+  WBC_QP_BWD(il, w, z);
   const A zf0 = s0 * z[0], zf1 = s1 * z[1], zf2 = s2 * z[2], zm0 = s3 * z[3], zm1 = s4 * z[4], zm2 = s5 * z[5];
   if constexpr (PRE) {   // G^-1, column by column (= row by row: symmetric): G x = e_c through the factor, zeros of e_c skipped by the compiler
     sfor<0, 6>([&](auto cc_) __attribute__((always_inline)) {
       constexpr int c = decltype(cc_)::value;
       if (!((cmask >> c) & 1)) return;      // (wavefront-uniform)
-      const A e0 = c == 0 ? (A)1 : (A)0, e1 = c == 1 ? (A)1 : (A)0, e2 = c == 2 ? (A)1 : (A)0, e3 = c == 3 ? (A)1 : (A)0, e4 = c == 4 ? (A)1 : (A)0,
-              e5 = c == 5 ? (A)1 : (A)0;
       A u[6], gc[6];
-      u[0] = e0 * il[0]; u[1] = e1 * il[1]; u[2] = e2 * il[2];
-      u[3] = (e3 - a01 * u[1] - a02 * u[2]) * il[3];
-      u[4] = (e4 - a10 * u[0] - a12 * u[2] - b10 * u[3]) * il[4];
-      u[5] = (e5 - a20 * u[0] - a21 * u[1] - b20 * u[3] - b21 * u[4]) * il[5];
-      gc[5] = u[5] * il[5];
-      gc[4] = (u[4] - b21 * gc[5]) * il[4];
-      gc[3] = (u[3] - b10 * gc[4] - b20 * gc[5]) * il[3];
-      gc[2] = (u[2] - a02 * gc[3] - a12 * gc[4]) * il[2];
-      gc[1] = (u[1] - a01 * gc[3] - a21 * gc[5]) * il[1];
-      gc[0] = (u[0] - a10 * gc[4] - a20 * gc[5]) * il[0];
+      WBC_QP_UNIT_SOLVE(A, c, u, gc);
 #pragma unroll
       for (int j = 0; j < 6; ++j) pre[6 * c + j] = (double)gc[j];
     });
@@ -140,18 +115,10 @@ WBC_DEV void qp_predict_part(const DevParams<T>& prm, const QpArgs<T>& a, unsign
     const A x1 = on ? zf1 + (zm2 * dx - zm0 * dz) : (A)0;
     const A x2 = on ? zf2 + (zm0 * dy - zm1 * dx) : (A)0;
     if constexpr (PRE) { pre[36 + 3 * f] = (double)x0; pre[36 + 3 * f + 1] = (double)x1; pre[36 + 3 * f + 2] = (double)x2; }
-    A nx = PLD(a.normals, 3 * f), ny = PLD(a.normals, 3 * f + 1), nz = PLD(a.normals, 3 * f + 2);
-    const A iln = rs(nx * nx + ny * ny + nz * nz);
-    nx *= iln; ny *= iln; nz *= iln;
-    const bool usex = fabs_t(nx) < (A)0.9;
-    const A rx = usex ? (A)1 : (A)0, ry = usex ? (A)0 : (A)1;
-    const A rd = rx * nx + ry * ny;
-    A t1x = rx - nx * rd, t1y = ry - ny * rd, t1z = -nz * rd;
-    const A it = rs(t1x * t1x + t1y * t1y + t1z * t1z);
-    t1x *= it; t1y *= it; t1z *= it;
-    const A t2x = ny * t1z - nz * t1y, t2y = nz * t1x - nx * t1z, t2z = nx * t1y - ny * t1x;
+    A nx = GLD(a.normals, 3 * f), ny = GLD(a.normals, 3 * f + 1), nz = GLD(a.normals, 3 * f + 2);
+    WBC_QP_CONTACT_BASIS(A, rs)
     const A fn = nx * x0 + ny * x1 + nz * x2, f1 = t1x * x0 + t1y * x1 + t1z * x2, f2 = t2x * x0 + t2y * x1 + t2z * x2;
-    const A mf = PLD(a.mu, f) * prm.mu_scale * fn, tol = -prm.qp_tol;
+    const A mf = GLD(a.mu, f) * prm.mu_scale * fn, tol = -prm.qp_tol;
     const A sl[6] = {mf - f1, mf + f1, mf - f2, mf + f2, fn - prm.fn_min, prm.fn_max - fn};
     int cnt = 0;
     A mg = 0;
@@ -166,8 +133,6 @@ WBC_DEV void qp_predict_part(const DevParams<T>& prm, const QpArgs<T>& a, unsign
   }
   out.cnt = cnt_all; out.mag = mag; out.fin_ok = fin_ok;
   out.zf0 = zf0; out.zf1 = zf1; out.zf2 = zf2; out.zm0 = zm0; out.zm1 = zm1; out.zm2 = zm2;
-#undef PLD_D
-#undef PLD
 }
 
 // a state whose x0 violates nothing: f = x0, tau = taup - rhat - Jc_leg^T f, status 0, no iterations (the epilogue of qp_struct16_body, one state per lane)
@@ -175,39 +140,35 @@ template <class T, bool RHAT, bool PRE = false>
 WBC_DEV void qp_predict_finish(const DevParams<T>& prm, const QpArgs<T>& a, const QpJidx& jmap, unsigned s32, unsigned N32,
                                const PredPart<typename PredA<T, PRE>::type>& pp) {
   using A = typename PredA<T, PRE>::type;
-#define PLD(ptr, comp) ((A)(*(const T*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T)))))
-#define PLD_D(f_, dx_, dy_, dz_) do { \
-    if (a.Jc) { dx_ = PLD(a.Jc, (3 * (f_) + 1) * 18 + 5); dy_ = PLD(a.Jc, (3 * (f_) + 2) * 18 + 3); dz_ = PLD(a.Jc, (3 * (f_)) * 18 + 4); } \
-    else { dx_ = PLD(a.ws, WS_D + 3 * (f_)); dy_ = PLD(a.ws, WS_D + 3 * (f_) + 1); dz_ = PLD(a.ws, WS_D + 3 * (f_) + 2); } } while (0)
+  using RowS = T;
+  using RowA = A;
   const int mask = a.mask[s32] & 0xF;
   const A zf0 = pp.zf0, zf1 = pp.zf1, zf2 = pp.zf2, zm0 = pp.zm0, zm1 = pp.zm1, zm2 = pp.zm2;
   {
-#define PST(ptr, comp, val) (*(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (T)(val))
 #pragma unroll 2
     for (int f = 0; f < 4; ++f) {
       const bool on = (mask >> f) & 1;
       A dx, dy, dz;
       PLD_D(f, dx, dy, dz);
       const A fx = on ? zf0 + (zm1 * dz - zm2 * dy) : (A)0, fy = on ? zf1 + (zm2 * dx - zm0 * dz) : (A)0, fz = on ? zf2 + (zm0 * dy - zm1 * dx) : (A)0;
-      PST(a.f, 3 * f, fx); PST(a.f, 3 * f + 1, fy); PST(a.f, 3 * f + 2, fz);
+      GST(a.f, 3 * f, fx); GST(a.f, 3 * f + 1, fy); GST(a.f, 3 * f + 2, fz);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const int jm = jmap.j[3 * f + k];
-        const A taup = PLD(a.ws, WS_TAUP + 3 * f + k) - (RHAT ? PLD(a.ws, WS_RHAT + 6 + 3 * f + k) : (A)0);
+        const A taup = GLD(a.ws, WS_TAUP + 3 * f + k) - (RHAT ? GLD(a.ws, WS_RHAT + 6 + 3 * f + k) : (A)0);
         A j0, j1, j2;
-        if (a.Jc) { j0 = PLD(a.Jc, (3 * f + 0) * 18 + 6 + jm); j1 = PLD(a.Jc, (3 * f + 1) * 18 + 6 + jm); j2 = PLD(a.Jc, (3 * f + 2) * 18 + 6 + jm); }
-        else { j0 = PLD(a.ws, WS_JCL + 9 * f + k); j1 = PLD(a.ws, WS_JCL + 9 * f + 3 + k); j2 = PLD(a.ws, WS_JCL + 9 * f + 6 + k); }
-        PST(a.tau, jm, taup - (j0 * fx + j1 * fy + j2 * fz));
+        if (a.Jc) { j0 = GLD(a.Jc, JC_LEG_WORD(f, 0, jm)); j1 = GLD(a.Jc, JC_LEG_WORD(f, 1, jm)); j2 = GLD(a.Jc, JC_LEG_WORD(f, 2, jm)); }
+        else { j0 = GLD(a.ws, WS_JCL + 9 * f + k); j1 = GLD(a.ws, WS_JCL + 9 * f + 3 + k); j2 = GLD(a.ws, WS_JCL + 9 * f + 6 + k); }
+        GST(a.tau, jm, taup - (j0 * fx + j1 * fy + j2 * fz));
       }
     }
     a.status[s32] = 0;
     if (a.iters) a.iters[s32] = 0;
     if (a.aset_out) a.aset_out[s32] = 0;   // the unconstrained minimum: the empty active set
-#undef PST
   }
-#undef PLD_D
-#undef PLD
 }
+
+#undef PLD_D
 
 // fitted on the bench data (least squares on the iteration count): 0.52 count + 0.70 ln(1 + summed violation); three
 // buckets per predicted iteration.  Sorting by it: 2.96 trips per group (count alone 3.25, perfect knowledge 2.51).
@@ -231,13 +192,13 @@ WBC_DEV int qp_predict_key(const DevParams<T>& prm, const QpArgs<T>& a, const Qp
 
 constexpr int WBC_QP_TILE_WAVES = 2;
 
-// DENSE (fp32 only): the orthogonal-factor body in fp32 arithmetic instead of the structured body in fp64 arithmetic.  At 117 VGPRs
+// DENSE (fp32 only): the orthogonal-factor body (qp_group16.hip.hpp) in fp32 arithmetic instead of the structured body in fp64 arithmetic.  At 117 VGPRs
 // four workgroups share a CU where the structured body's 183 allow two: from ~49 152 fp32 states on (more than two tiles of 64 per
 // CU) the dense body wins (65 536: 38 vs 46 us, 131 072: 72 vs 92 us), below it loses (32 768: 26.0 vs 23.4 us).  Measured, MI355X.
 template <class T, bool RHAT, int TILE, bool DENSE = false>
 __global__ __launch_bounds__(256, (DENSE ? 4 : WBC_QP_TILE_WAVES)) void qp_tile_kernel(DevParams<T> prm, QpArgs<T> a, QpJidx jmap) {
   static_assert(TILE % 4 == 0 && TILE <= 1024, "tile of whole four-state groups");
-  constexpr bool PRE = (std::is_same<T, double>::value) && !DENSE && TILE <= 64 && (true || (false && std::is_same<T, double>::value));
+  constexpr bool PRE = (std::is_same<T, double>::value) && !DENSE && TILE <= 64;
   __shared__ double pre[PRE ? TILE * QP_PRE_WORDS : 1];
   __shared__ unsigned short order[TILE];
   __shared__ int hist[64];
@@ -305,7 +266,7 @@ __global__ __launch_bounds__(256, (DENSE ? 4 : WBC_QP_TILE_WAVES)) void qp_tile_
     const bool live = 4 * g + row < nsolve;
     const unsigned oi = order[live ? 4 * g + row : 0];
     const size_t s = base + oi;
-    if constexpr (DENSE) qp_group16_body<T, false, RHAT, 16, true>(prm, a, jmap, nullptr, nullptr, QpWho{live ? s : (size_t)0, live});
+    if constexpr (DENSE) qp_group16_body<T, RHAT>(prm, a, QpWho{live ? s : (size_t)0, live});
     else qp_body<T, false, RHAT, 16, true, 4, QpNoIdle, PRE>(prm, a, jmap, nullptr, nullptr, QpWho{live ? s : (size_t)0, live, pre + (PRE ? oi * QP_PRE_WORDS : 0)});
 #ifdef WBC_TILE_STAMP
     if (ts_ng == 0) TSTAMP(ts_g1);
@@ -358,6 +319,8 @@ constexpr bool stile_fin_default(bool is_float) { return (is_float); }
 template <class T, bool RHAT, int NW, int CH, bool FIN = stile_fin_default(std::is_same<T, float>::value), bool HAND = false>
 WBC_DEV void qp_stile_body(const DevParams<T>& prm, const QpArgs<T>& a, const QpJidx& jmap, int tile, unsigned blk, unsigned char* smem, unsigned wave_in, const T* hand = nullptr) {
   using A = T;   // (the caller sizes the tile: 4 tile <= 64 NW, one predictor thread per foot and state)
+  using RowS = T;
+  using RowA = T;
   const int ST = tile | 1;   // row stride of the image: the sixteen lanes of a row read sixteen ROWS of one column -- an odd stride spreads them over the banks
   S16Lds<double>* const tabs = (S16Lds<double>*)smem;   // [NW] solver tables, one per wavefront
   T* const img = (T*)(tabs + NW);
@@ -411,19 +374,19 @@ WBC_DEV void qp_stile_body(const DevParams<T>& prm, const QpArgs<T>& a, const Qp
         else if constexpr (su < 46) {
           constexpr unsigned v = su - 34, f = v / 3, c = v - 3 * f;
           ptr = gsrc;
-          comp = jc ? (c == 0 ? (3 * f + 1) * 18 + 5 : (c == 1 ? (3 * f + 2) * 18 + 3 : (3 * f) * 18 + 4)) : (unsigned)WS_D + v;
+          comp = jc ? JC_LEVER_WORD(f, (int)c) : (unsigned)WS_D + v;
         } else {
           constexpr unsigned r = su - 46, f = r / 9, mm = (r - 9 * f) / 3, k = r - 9 * f - 3 * mm;
           const unsigned jm = (unsigned)((a.jpack >> (4 * (3 * f + k))) & 15u);
           ptr = gsrc;
-          comp = jc ? (3 * f + mm) * 18 + 6 + jm : (unsigned)WS_JCL + r;
+          comp = jc ? JC_LEG_WORD(f, mm, jm) : (unsigned)WS_JCL + r;
         }
         const unsigned hcol = col < (unsigned)tile ? col : (unsigned)tile - 1u;
         if constexpr (HAND && su >= 6 && su < 18) val[j] = hand[((unsigned)HAND_TAUP + su - 6) * (unsigned)tile + hcol];
-        else val[j] = *(const T*)((const char*)ptr + (size_t)((comp * N32 + sidx) * (unsigned)sizeof(T)));
+        else val[j] = GLD_AT(ptr, comp, sidx);
         if constexpr (RHAT && su < 18) {
           if constexpr (HAND) sub[j] = hand[((unsigned)HAND_RHAT + su) * (unsigned)tile + hcol];
-          else sub[j] = *(const T*)((const char*)a.ws + (size_t)((((unsigned)WS_RHAT + su) * N32 + sidx) * (unsigned)sizeof(T)));
+          else sub[j] = GLD_AT(a.ws, (unsigned)WS_RHAT + su, sidx);
         } else sub[j] = 0;
       });
       if constexpr (W == NW - 1) sfor<0, CH>([&](auto c_) __attribute__((always_inline)) {
@@ -478,35 +441,14 @@ WBC_DEV void qp_stile_body(const DevParams<T>& prm, const QpArgs<T>& a, const Qp
     A bt[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) bt[k] = IMGR(ST_B + k);
-    const A g00 = prm.alpha + s0 * s0 * nc, g11 = prm.alpha + s1 * s1 * nc, g22 = prm.alpha + s2 * s2 * nc;
-    const A gm01 = -(s3 * s1) * sz, gm02 = (s3 * s2) * sy, gm10 = (s4 * s0) * sz, gm12 = -(s4 * s2) * sx, gm20 = -(s5 * s0) * sy, gm21 = (s5 * s1) * sx;
-    const A m00 = prm.alpha + (s3 * s3) * (Pyy + Pzz), m11 = prm.alpha + (s4 * s4) * (Pxx + Pzz), m22 = prm.alpha + (s5 * s5) * (Pxx + Pyy);
-    const A m10 = -(s4 * s3) * Pxy, m20 = -(s5 * s3) * Pxz, m21 = -(s5 * s4) * Pyz;
     auto rs = [](A x) __attribute__((always_inline)) -> A {
       if constexpr (FIN) return rsqrt_nr(x);
       else if constexpr (std::is_same<A, double>::value) return __builtin_amdgcn_rsq(x); else return __builtin_amdgcn_rsqf(x);
     };
-    A il[6];
-    il[0] = rs(g00); il[1] = rs(g11); il[2] = rs(g22);
-    const A a01 = gm01 * il[1], a02 = gm02 * il[2], a10 = gm10 * il[0], a12 = gm12 * il[2], a20 = gm20 * il[0], a21 = gm21 * il[1];
-    const A c00 = m00 - a01 * a01 - a02 * a02, c11 = m11 - a10 * a10 - a12 * a12, c22 = m22 - a20 * a20 - a21 * a21;
-    const A c10 = m10 - a12 * a02, c20 = m20 - a21 * a01, c21 = m21 - a20 * a10;
-    il[3] = rs(c00);
-    const A b10 = c10 * il[3], b20 = c20 * il[3];
-    il[4] = rs(c11 - b10 * b10);
-    const A b21 = (c21 - b20 * b10) * il[4];
-    il[5] = rs(c22 - b20 * b20 - b21 * b21);
+    WBC_QP_G_FACTOR(A, rs, prm.alpha)
     A w[6], z[6];   // z = G^-1 S^(1/2) b
-    w[0] = s0 * bt[0] * il[0]; w[1] = s1 * bt[1] * il[1]; w[2] = s2 * bt[2] * il[2];
-    w[3] = (s3 * bt[3] - a01 * w[1] - a02 * w[2]) * il[3];
-    w[4] = (s4 * bt[4] - a10 * w[0] - a12 * w[2] - b10 * w[3]) * il[4];
-    w[5] = (s5 * bt[5] - a20 * w[0] - a21 * w[1] - b20 * w[3] - b21 * w[4]) * il[5];
-    z[5] = w[5] * il[5];
-    z[4] = (w[4] - b21 * z[5]) * il[4];
-    z[3] = (w[3] - b10 * z[4] - b20 * z[5]) * il[3];
-    z[2] = (w[2] - a02 * z[3] - a12 * z[4]) * il[2];
-    z[1] = (w[1] - a01 * z[3] - a21 * z[5]) * il[1];
-    z[0] = (w[0] - a10 * z[4] - a20 * z[5]) * il[0];
+    WBC_QP_FWD(il, s0 * bt[0], s1 * bt[1], s2 * bt[2], s3 * bt[3], s4 * bt[4], s5 * bt[5], w);
+    WBC_QP_BWD(il, w, z);
     const A zf0 = s0 * z[0], zf1 = s1 * z[1], zf2 = s2 * z[2], zm0 = s3 * z[3], zm1 = s4 * z[4], zm2 = s5 * z[5];
     // my foot: x0 = on (s_f z_f + (s_m z_m) x d), its six slacks
     const bool on = (mask >> fo) & 1;
@@ -515,15 +457,7 @@ WBC_DEV void qp_stile_body(const DevParams<T>& prm, const QpArgs<T>& a, const Qp
     x1 = on ? zf1 + (zm2 * dx - zm0 * dz) : (A)0;
     x2 = on ? zf2 + (zm0 * dy - zm1 * dx) : (A)0;
     A nx = IMGR(ST_N + 3 * fo), ny = IMGR(ST_N + 3 * fo + 1), nz = IMGR(ST_N + 3 * fo + 2);
-    const A iln = rs(nx * nx + ny * ny + nz * nz);
-    nx *= iln; ny *= iln; nz *= iln;
-    const bool usex = fabs_t(nx) < (A)0.9;
-    const A rx = usex ? (A)1 : (A)0, ry = usex ? (A)0 : (A)1;
-    const A rd = rx * nx + ry * ny;
-    A t1x = rx - nx * rd, t1y = ry - ny * rd, t1z = -nz * rd;
-    const A it = rs(t1x * t1x + t1y * t1y + t1z * t1z);
-    t1x *= it; t1y *= it; t1z *= it;
-    const A t2x = ny * t1z - nz * t1y, t2y = nz * t1x - nx * t1z, t2z = nx * t1y - ny * t1x;
+    WBC_QP_CONTACT_BASIS(A, rs)
     const A fn = nx * x0 + ny * x1 + nz * x2, f1 = t1x * x0 + t1y * x1 + t1z * x2, f2 = t2x * x0 + t2y * x1 + t2z * x2;
     const A mf = IMGR(ST_MU + fo) * prm.mu_scale * fn, tol = -prm.qp_tol;
     const A sl[6] = {mf - f1, mf + f1, mf - f2, mf + f2, fn - prm.fn_min, prm.fn_max - fn};
@@ -604,8 +538,8 @@ WBC_DEV void qp_stile_body(const DevParams<T>& prm, const QpArgs<T>& a, const Qp
       const unsigned col = ch * 64 + lane;
       if (r < 27u && col < (unsigned)tile && base + col < N) {
         const unsigned sidx = (unsigned)(base + col);
-        if (r < 12) *(T*)((char*)a.f + (size_t)((r * N32 + sidx) * (unsigned)sizeof(T))) = img[(ST_F + r) * ST + col];
-        else if (r < 24) *(T*)((char*)a.tau + (size_t)(((r - 12) * N32 + sidx) * (unsigned)sizeof(T))) = img[(ST_TAU + r - 12) * ST + col];
+        if (r < 12) GST_AT(a.f, r, sidx, img[(ST_F + r) * ST + col]);
+        else if (r < 24) GST_AT(a.tau, r - 12, sidx, img[(ST_TAU + r - 12) * ST + col]);
         else if (r == 24) a.status[sidx] = iimg[tile + col];
 #ifdef WBC_TILE_STAMP   // (the stamp build returns its stamps through `iters`)
         else if (r == 25) {}

@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "device_types.hpp"
-#include "qp_group16.hip.hpp"   // rsqrt_nr / rcp_nr, Lim, WBC_DEV
+#include "qp_row16.hip.hpp"   // rsqrt_nr / rcp_nr, Lim, the address form, the contact tangent, the words of Jc
 
 namespace wbc {
 
@@ -84,9 +84,7 @@ WBC_DEV float qpl_refine(float seed, float) { return seed; }
 // first tangent of the contact frame from the unit normal (the oracle's convention: e_x, or e_y for a normal along x, made
 // orthogonal to n); `it` = 1 / its length before normalisation
 template <class T> WBC_DEV void qpl_tangent(const T* n, T it, T* t1) {
-  const bool usex = fabs_t(n[0]) < (T)0.9;
-  const T rx = usex ? (T)1 : (T)0, ry = usex ? (T)0 : (T)1;
-  const T rd = rx * n[0] + ry * n[1];
+  WBC_QP_TANGENT_AXIS(T, n[0], n[1])
   t1[0] = (rx - n[0] * rd) * it; t1[1] = (ry - n[1] * rd) * it; t1[2] = (-n[2] * rd) * it;
 }
 
@@ -310,23 +308,23 @@ __global__ __launch_bounds__(QPL_WG, (sizeof(T) == 4 ? QPL_F32_WAVES : QPL_F64_W
   const size_t s_raw = (size_t)blockIdx.x * QPL_WG + tid;
   const bool live = s_raw < N;
   const unsigned s32 = (unsigned)(live ? s_raw : N - 1);
-#define LLD(ptr, comp) (*(const T*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))))
-#define LST(ptr, comp, val) (*(T*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(T))) = (val))
+  using RowS = T;
+  using RowA = T;
   const int mask = a.mask[s32] & 0xF;
   const bool geom_jc = a.Jc != nullptr;
   // every input of the solve is requested before the first one is used: a load that waits exposes its whole latency
   T in_d[12], in_n[12], in_mu[4], in_b[6], in_r[6];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    if (geom_jc) { in_d[3 * k] = LLD(a.Jc, (3 * k + 1) * 18 + 5); in_d[3 * k + 1] = LLD(a.Jc, (3 * k + 2) * 18 + 3); in_d[3 * k + 2] = LLD(a.Jc, (3 * k) * 18 + 4); }
-    else { in_d[3 * k] = LLD(a.ws, WS_D + 3 * k); in_d[3 * k + 1] = LLD(a.ws, WS_D + 3 * k + 1); in_d[3 * k + 2] = LLD(a.ws, WS_D + 3 * k + 2); }
+    if (geom_jc) { in_d[3 * k] = GLD(a.Jc, JC_LEVER_WORD(k, 0)); in_d[3 * k + 1] = GLD(a.Jc, JC_LEVER_WORD(k, 1)); in_d[3 * k + 2] = GLD(a.Jc, JC_LEVER_WORD(k, 2)); }
+    else { in_d[3 * k] = GLD(a.ws, WS_D + 3 * k); in_d[3 * k + 1] = GLD(a.ws, WS_D + 3 * k + 1); in_d[3 * k + 2] = GLD(a.ws, WS_D + 3 * k + 2); }
   }
 #pragma unroll
-  for (int c = 0; c < 12; ++c) in_n[c] = LLD(a.normals, c);
+  for (int c = 0; c < 12; ++c) in_n[c] = GLD(a.normals, c);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) in_mu[k] = LLD(a.mu, k);
+  for (int k = 0; k < 4; ++k) in_mu[k] = GLD(a.mu, k);
 #pragma unroll
-  for (int c = 0; c < 6; ++c) { in_b[c] = a.wdes ? LLD(a.wdes, c) : LLD(a.ws, WS_B + c); in_r[c] = RHAT ? LLD(a.ws, WS_RHAT + c) : (T)0; }
+  for (int c = 0; c < 6; ++c) { in_b[c] = a.wdes ? GLD(a.wdes, c) : GLD(a.ws, WS_B + c); in_r[c] = RHAT ? GLD(a.ws, WS_RHAT + c) : (T)0; }
   // (the empty asm statements keep the compiler from sinking a load down to its first use)
 #pragma unroll
   for (int c = 0; c < 12; ++c) { asm volatile("" : "+v"(in_d[c])); asm volatile("" : "+v"(in_n[c])); }
@@ -412,9 +410,9 @@ __global__ __launch_bounds__(QPL_WG, (sizeof(T) == 4 ? QPL_F32_WAVES : QPL_F64_W
       for (int j = 0; j < 3; ++j) {
         const int jm = jmap.j[3 * k + j];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) jl[9 * k + 3 * j + c] = geom_jc ? LLD(a.Jc, (3 * k + c) * 18 + 6 + jm) : LLD(a.ws, WS_JCL + 9 * k + 3 * c + j);
-        tp[3 * k + j] = LLD(a.ws, WS_TAUP + 3 * k + j);
-        tr[3 * k + j] = RHAT ? LLD(a.ws, WS_RHAT + 6 + 3 * k + j) : (T)0;
+        for (int c = 0; c < 3; ++c) jl[9 * k + 3 * j + c] = geom_jc ? GLD(a.Jc, JC_LEG_WORD(k, c, jm)) : GLD(a.ws, WS_JCL + 9 * k + 3 * c + j);
+        tp[3 * k + j] = GLD(a.ws, WS_TAUP + 3 * k + j);
+        tr[3 * k + j] = RHAT ? GLD(a.ws, WS_RHAT + 6 + 3 * k + j) : (T)0;
       }
     // the forces at the solution go to LDS while those loads are in flight (the frames live in LDS: there are registers to spare)
     qpl_eval<T, true>(L, tid, mask, sS, ralpha, fmin, fmax, beta, e, code, F);
@@ -426,10 +424,10 @@ __global__ __launch_bounds__(QPL_WG, (sizeof(T) == 4 ? QPL_F32_WAVES : QPL_F64_W
     for (int k = 0; k < 4; ++k) {
       const T fw[3] = {L.n[0][k][tid], L.n[1][k][tid], L.n[2][k][tid]};
 #pragma unroll
-      for (int c = 0; c < 3; ++c) LST(a.f, 3 * k + c, fw[c]);
+      for (int c = 0; c < 3; ++c) GST(a.f, 3 * k + c, fw[c]);
 #pragma unroll
       for (int j = 0; j < 3; ++j)   // tau of joint j of leg k = tau_partial - (own-leg Jacobian column) . f
-        LST(a.tau, jmap.j[3 * k + j], (tp[3 * k + j] - tr[3 * k + j]) - (jl[9 * k + 3 * j] * fw[0] + jl[9 * k + 3 * j + 1] * fw[1] + jl[9 * k + 3 * j + 2] * fw[2]));
+        GST(a.tau, jmap.j[3 * k + j], (tp[3 * k + j] - tr[3 * k + j]) - (jl[9 * k + 3 * j] * fw[0] + jl[9 * k + 3 * j + 1] * fw[1] + jl[9 * k + 3 * j + 2] * fw[2]));
     }
     a.status[s32] = 0;
     if (a.iters) a.iters[s32] = iters;
@@ -439,8 +437,6 @@ __global__ __launch_bounds__(QPL_WG, (sizeof(T) == 4 ? QPL_F32_WAVES : QPL_F64_W
     if (slot < (int)a.N) todo[4 + slot] = (int)s32;   // (always, while the count starts a tick at zero: the guard keeps a stale count from writing past the list)
     else { a.status[s32] = 1; if (a.iters) a.iters[s32] = iters; }   // list overflow (the count did not start at zero): reported, never silent -- tau, f of this state are NOT this tick's
   }
-#undef LLD
-#undef LST
 }
 
 }  // namespace wbc

@@ -1,6 +1,7 @@
 // GRF QP + torque map, round 3: the SAME dual active-set method (Goldfarb-Idnani, same pivoting rules, tolerances and status
 // codes as qp_group16.hip.hpp and the oracle) with all its linear algebra done on the 6-dimensional WRENCH space instead of on
-// 12 x 12 factors.  fp64 only (the inverse below is kept by Sherman-Morrison updates; fp32 keeps the orthogonal-factor form).
+// 12 x 12 factors.  fp64 arithmetic only (the inverse below is kept by Sherman-Morrison updates), for both scalar types of the batch arrays: every
+// QP kernel runs this body except large fp32 tiles, which keep the orthogonal-factor form in fp32 arithmetic (qp_group16.hip.hpp).
 //
 //     min 1/2 alpha |f|^2 + 1/2 |B f - beta|^2,   B = S^(1/2) [I ; [d_k]x] per stance foot,   s.t. per-foot pyramid + box
 //
@@ -21,9 +22,9 @@
 // a Householder update of two copies of J and a back-substitution (round 2 stamps); this form needs one 6 x 6 matrix-vector
 // product, a handful of 3-vector operations per lane and no factor update beyond a rank-one FMA per row.
 //
-// Mapping (same as qp_group16: one QP per 16-lane DPP row, four per wavefront; lane 4k + c of a row belongs to foot k):
+// Mapping (qp_row16.hip.hpp: one QP per 16-lane DPP row, four per wavefront; lane 4k + c of a row belongs to foot k):
 //   lane 4k + c, c < 3: variable (foot k, axis c); row c of P_k; slot c of foot k's active list (constraint id, multiplier,
-//                       row c of N_k^+); constraints 2 (4k + c) and 2 (4k + c) + 1 as in qp_group16
+//                       row c of N_k^+); constraints 2 (4k + c) and 2 (4k + c) + 1 (WBC_QP_FORM_ROWS)
 //   lane i < 6 (and i + 6, i + 12): row i of G_A^-1   (y_i = row . b, then six row broadcasts from static lanes)
 //   LDS per QP: the 32 constraint normals (by id), P_k (6 words per foot) and d_k for the run-time foot index kp -- every lane
 //   fetches n+, P_kp, d_kp and forms v, b redundantly, so the step needs NO cross-lane reduction at all.
@@ -31,7 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "device_types.hpp"
-#include "qp_group16.hip.hpp"
+#include "qp_row16.hip.hpp"
 
 namespace wbc {
 
@@ -42,57 +43,26 @@ template <class T> struct S16Lds { T C[4][32 * 3]; T P[4][4 * 16]; T D[4][4 * 3]
 // wavefront starts over).  A function of explicit arguments, not a capturing lambda: called from two places, a closure object would sit on the stack.
 template <class T>
 WBC_DEV void s16_cold_inverse_row(int mask, T d_me, T alpha_l, T s0, T s1, T s2, T s3, T s4, T s5, int gi, T (&Gr)[6]) {
-  T a01, a02, a10, a12, a20, a21, b10, b20, b21;
-  T il[6];
-  {
-    T Dx[4], Dy[4], Dz[4], Of[4];
-    sfor<0, 4>([&](auto fc) __attribute__((always_inline)) {
-      constexpr int fj = decltype(fc)::value;
-      const bool onj = (mask >> fj) & 1;
-      Of[fj] = onj ? (T)1 : (T)0;
-      Dx[fj] = onj ? gbc<3 * fj>(d_me) : (T)0; Dy[fj] = onj ? gbc<3 * fj + 1>(d_me) : (T)0; Dz[fj] = onj ? gbc<3 * fj + 2>(d_me) : (T)0;
-    });
-    const T nc = (Of[0] + Of[1]) + (Of[2] + Of[3]);
-    const T sx = (Dx[0] + Dx[1]) + (Dx[2] + Dx[3]), sy = (Dy[0] + Dy[1]) + (Dy[2] + Dy[3]), sz = (Dz[0] + Dz[1]) + (Dz[2] + Dz[3]);
-    T Pxx = 0, Pxy = 0, Pxz = 0, Pyy = 0, Pyz = 0, Pzz = 0;
-    sfor<0, 4>([&](auto fc) __attribute__((always_inline)) {
-      constexpr int fj = decltype(fc)::value;
-      Pxx += Dx[fj] * Dx[fj]; Pxy += Dx[fj] * Dy[fj]; Pxz += Dx[fj] * Dz[fj];
-      Pyy += Dy[fj] * Dy[fj]; Pyz += Dy[fj] * Dz[fj]; Pzz += Dz[fj] * Dz[fj];
-    });
-    const T g00 = alpha_l + s0 * s0 * nc, g11 = alpha_l + s1 * s1 * nc, g22 = alpha_l + s2 * s2 * nc;
-    const T gm01 = -(s3 * s1) * sz, gm02 = (s3 * s2) * sy, gm10 = (s4 * s0) * sz, gm12 = -(s4 * s2) * sx, gm20 = -(s5 * s0) * sy, gm21 = (s5 * s1) * sx;
-    const T m00 = alpha_l + (s3 * s3) * (Pyy + Pzz), m11 = alpha_l + (s4 * s4) * (Pxx + Pzz), m22 = alpha_l + (s5 * s5) * (Pxx + Pyy);
-    const T m10 = -(s4 * s3) * Pxy, m20 = -(s5 * s3) * Pxz, m21 = -(s5 * s4) * Pyz;
-    il[0] = rsqrt_nr(g00); il[1] = rsqrt_nr(g11); il[2] = rsqrt_nr(g22);
-    a01 = gm01 * il[1]; a02 = gm02 * il[2]; a10 = gm10 * il[0]; a12 = gm12 * il[2]; a20 = gm20 * il[0]; a21 = gm21 * il[1];
-    const T c00 = m00 - a01 * a01 - a02 * a02, c11 = m11 - a10 * a10 - a12 * a12, c22 = m22 - a20 * a20 - a21 * a21;
-    const T c10 = m10 - a12 * a02, c20 = m20 - a21 * a01, c21 = m21 - a20 * a10;
-    il[3] = rsqrt_nr(c00);
-    b10 = c10 * il[3]; b20 = c20 * il[3];
-    const T t11 = c11 - b10 * b10;
-    il[4] = rsqrt_nr(t11);
-    b21 = (c21 - b20 * b10) * il[4];
-    const T t22 = c22 - b20 * b20 - b21 * b21;
-    il[5] = rsqrt_nr(t22);
-  }
+  T Dx[4], Dy[4], Dz[4], Of[4];
+  sfor<0, 4>([&](auto fc) __attribute__((always_inline)) {
+    constexpr int fj = decltype(fc)::value;
+    const bool onj = (mask >> fj) & 1;
+    Of[fj] = onj ? (T)1 : (T)0;
+    Dx[fj] = onj ? gbc<3 * fj>(d_me) : (T)0; Dy[fj] = onj ? gbc<3 * fj + 1>(d_me) : (T)0; Dz[fj] = onj ? gbc<3 * fj + 2>(d_me) : (T)0;
+  });
+  const T nc = (Of[0] + Of[1]) + (Of[2] + Of[3]);
+  const T sx = (Dx[0] + Dx[1]) + (Dx[2] + Dx[3]), sy = (Dy[0] + Dy[1]) + (Dy[2] + Dy[3]), sz = (Dz[0] + Dz[1]) + (Dz[2] + Dz[3]);
+  T Pxx = 0, Pxy = 0, Pxz = 0, Pyy = 0, Pyz = 0, Pzz = 0;
+  sfor<0, 4>([&](auto fc) __attribute__((always_inline)) {
+    constexpr int fj = decltype(fc)::value;
+    Pxx += Dx[fj] * Dx[fj]; Pxy += Dx[fj] * Dy[fj]; Pxz += Dx[fj] * Dz[fj];
+    Pyy += Dy[fj] * Dy[fj]; Pyz += Dy[fj] * Dz[fj]; Pzz += Dz[fj] * Dz[fj];
+  });
+  WBC_QP_G_FACTOR(T, rsqrt_nr, alpha_l)
   // ------------------------------------------------------------------ my row of G^-1 (row gi = l16 mod 6): G x = e_gi by the factor
-  {
-    const T e0 = gi == 0 ? (T)1 : (T)0, e1 = gi == 1 ? (T)1 : (T)0, e2 = gi == 2 ? (T)1 : (T)0, e3 = gi == 3 ? (T)1 : (T)0, e4 = gi == 4 ? (T)1 : (T)0,
-            e5 = gi == 5 ? (T)1 : (T)0;
-    T w[6];
-    w[0] = e0 * il[0]; w[1] = e1 * il[1]; w[2] = e2 * il[2];
-    w[3] = (e3 - a01 * w[1] - a02 * w[2]) * il[3];
-    w[4] = (e4 - a10 * w[0] - a12 * w[2] - b10 * w[3]) * il[4];
-    w[5] = (e5 - a20 * w[0] - a21 * w[1] - b20 * w[3] - b21 * w[4]) * il[5];
-    Gr[5] = w[5] * il[5];
-    Gr[4] = (w[4] - b21 * Gr[5]) * il[4];
-    Gr[3] = (w[3] - b10 * Gr[4] - b20 * Gr[5]) * il[3];
-    Gr[2] = (w[2] - a02 * Gr[3] - a12 * Gr[4]) * il[2];
-    Gr[1] = (w[1] - a01 * Gr[3] - a21 * Gr[5]) * il[1];
-    Gr[0] = (w[0] - a10 * Gr[4] - a20 * Gr[5]) * il[0];
-  }
-  }
+  T w[6];
+  WBC_QP_UNIT_SOLVE(T, gi, w, Gr);
+}
 
 // TS = the solver's scalar type (what the batch arrays and the LDS workspace hold); the arithmetic is ALWAYS double: the inverse
 // is kept by rank-one updates (cond(G_A) ~ 1e4-1e5 is too much for fp32), and on gfx950 a dependent v_fma_f64 costs a lone
@@ -116,6 +86,8 @@ template <class TS, bool WSLDS, bool RHAT = false, int SPW = 16, bool TILED = fa
 WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, const QpJidx& jmap, const TS* wsl, const QpSync* sync = nullptr,
                               const QpWho who = QpWho{0, false}, Idle idle = Idle(), int* carry = nullptr) {
   using T = double;
+  using RowS = TS;
+  using RowA = T;
   static_assert(!(WSLDS && TILED), "tiles are dealt by the stand-alone kernel only");
   static_assert(STG == 0 || (TILED && WARM == 0 && !RHAT), "staged tiles: cold, rhat folded into the image");
   // SPEC (fused / rollout kernels with the observer on, cold start): the target wrench b = w_des - rhat_base is the last input to arrive -- the observer
@@ -128,15 +100,7 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   // strictly convex, so f, tau, status do not depend on b~ at all -- a torn or already updated read of r_prev only makes the guess better or worse.
   constexpr bool SPEC = WSLDS && RHAT && WARM == 0 && !PRE && !TILED;
   static_assert(!(WARM != 0 && PRE), "warm starts set their blocks up themselves");
-  unsigned tx = threadIdx.x;
-  asm volatile("" : "+v"(tx));   // lane-derived predicates stay inside this call (see WBC_LAUNDERED_TID, lane_rows.hip.hpp)
-  const int lane = tx & 63;
-  const int l16 = lane & 15;
-  const int rowbase = lane & 48;
-  const int grp = lane >> 4;
-  const int f = l16 >> 2, c3 = l16 & 3;
-  const bool isvar = c3 < 3;
-  const int v = 3 * f + (isvar ? c3 : 0);
+  WBC_QP_ROW_PROLOGUE
   S16Lds<T>* Lp;
   if constexpr (STG != 0) Lp = (S16Lds<T>*)who.tab;     // (staged tiles: this wavefront's tables live in the kernel's dynamic LDS, beside the image)
   else { __shared__ S16Lds<T> lds_all[WPB]; Lp = &lds_all[tx >> 6]; }
@@ -148,16 +112,17 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   const size_t N = a.N;
   const unsigned N32 = (unsigned)N;
   size_t wg = blockIdx.x;
-  if (WPB == 1 && (gridDim.x & 31) == 0) wg = (wg & ~(size_t)31) + ((wg & 7) << 2) + ((wg >> 3) & 3);   // XCD-aware (qp_group16.hip.hpp)
+  // One-wave workgroups (stand-alone kernel): every wavefront is its own workgroup, so its LDS and wave slot are released the moment ITS four QPs
+  // are done and the CU backfills.  XCD-aware order for them: workgroups b, b+8, b+16, b+24 land on the same XCD (round-robin dispatch) and take
+  // four CONSECUTIVE 4-state groups = one whole 128-byte line per component row.  Speed only.
+  if (WPB == 1 && (gridDim.x & 31) == 0) wg = (wg & ~(size_t)31) + ((wg & 7) << 2) + ((wg >> 3) & 3);
   static_assert(SPW == 16 || WSLDS, "fewer states per workgroup only inside the fused kernels");
   const size_t qp_raw = TILED ? who.state : WSLDS ? (size_t)blockIdx.x * SPW + (tx >> 4) : (wg * blockDim.x + tx) >> 4;
   bool live = TILED ? who.live : (qp_raw < N && (SPW == 16 || (int)(tx >> 4) < SPW));
   unsigned s32 = (unsigned)(live ? qp_raw : N - 1);
   const T INF = Lim<T>::inf, EPS = Lim<T>::eps;
-#define GLD(ptr, comp) ((T)(*(const TS*)((const char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(TS)))))
 #define WSLD(comp) (WSLDS ? (T)wsl[(comp) * 16 + (int)(tx >> 4)] : GLD(a.ws, comp))
 #define BLD(c) (WSLDS ? (T)wsl[(WS_B + (c)) * 16 + (int)(tx >> 4)] : (a.wdes ? GLD(a.wdes, c) : GLD(a.ws, WS_B + (c))))
-#define GST(ptr, comp, val) (*(TS*)((char*)(ptr) + (size_t)(((unsigned)(comp) * N32 + s32) * (unsigned)sizeof(TS))) = (TS)(val))
   const int stg_slot = (STG != 0 && live) ? who.slot : 0;
 #define IMG(comp) (((TS*)who.img)[(comp) * who.stride + stg_slot])
 
@@ -178,42 +143,23 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   if constexpr (WARM == 2) aset = *carry;
   WBC_QSTAMP(1);
   idle();
-  // ------------------------------------------------------------------ my constraints (friction pyramid, force box): as in qp_group16_body.
+  // ------------------------------------------------------------------ my constraints (friction pyramid, force box): WBC_QP_FORM_ROWS, qp_row16.hip.hpp.
   // They need the normals and mu only: the kernels that wait for the lever arms (WSLDS: one-launch tick, rollouts) form them in front of that wait
   // (13.3 -> 13.2 us at 4 096 states; -DWBC_QP_CONS_EARLY=0: behind the factor, as the stand-alone kernels keep it -- there the early form costs 0.8 %)
   constexpr bool CONS_EARLY = WSLDS && WARM == 0;   // (the warm observer-on tick sits at 255 registers: the rows held across the wait spill there)
   T cAx, cAy, cAz, rA, cBx = 0, cBy = 0, cBz = 0;
   const bool hasB = c3 < 2;
-#define WBC_QP_FORM_ROWS do { \
-    T nx = dppx<0x00>(n_ld), ny = dppx<0x55>(n_ld), nz = dppx<0xAA>(n_ld); \
-    const T iln = rsqrt_nr(nx * nx + ny * ny + nz * nz); \
-    nx *= iln; ny *= iln; nz *= iln; \
-    const bool usex = fabs_t(nx) < (T)0.9; \
-    const T rx = usex ? (T)1 : (T)0, ry = usex ? (T)0 : (T)1; \
-    const T rd = rx * nx + ry * ny; \
-    T t1x = rx - nx * rd, t1y = ry - ny * rd, t1z = -nz * rd; \
-    const T it = rsqrt_nr(t1x * t1x + t1y * t1y + t1z * t1z); \
-    t1x *= it; t1y *= it; t1z *= it; \
-    const T t2x = ny * t1z - nz * t1y, t2y = nz * t1x - nx * t1z, t2z = nx * t1y - ny * t1x; \
-    const T mt = mu_f * prm.mu_scale; \
-    const T ttx = (c3 == 0) ? t1x : t2x, tty = (c3 == 0) ? t1y : t2y, ttz = (c3 == 0) ? t1z : t2z; \
-    if (hasB) { \
-      cAx = mt * nx - ttx; cAy = mt * ny - tty; cAz = mt * nz - ttz; rA = 0; \
-      cBx = mt * nx + ttx; cBy = mt * ny + tty; cBz = mt * nz + ttz; \
-    } else if (c3 == 2) { cAx = nx; cAy = ny; cAz = nz; rA = prm.fn_min; } \
-    else { cAx = -nx; cAy = -ny; cAz = -nz; rA = -prm.fn_max; } \
-  } while (0)
   if constexpr (CONS_EARLY) WBC_QP_FORM_ROWS;
   if constexpr (WSLDS) { if (sync) qp_wait(sync->geom, sync->need_geom); }
   WBC_QSTAMP(2);
   T d_me = 0;
   if constexpr (STG != 0) { if (isvar) d_me = (T)IMG(ST_D + v); }
   else if (geom_jc) {
-    const int comp = c3 == 0 ? (3 * f + 1) * 18 + 5 : (c3 == 1 ? (3 * f + 2) * 18 + 3 : (3 * f) * 18 + 4);
+    const int comp = JC_LEVER_WORD(f, c3);
     if (isvar) d_me = GLD(a.Jc, comp);
   } else if (isvar) d_me = WSLD(WS_D + v);
 
-  // ------------------------------------------------------------------ G = alpha I + B B^T and its factor (as in qp_group16_body)
+  // ------------------------------------------------------------------ G = alpha I + B B^T and its factor (WBC_QP_G_FACTOR, qp_row16.hip.hpp)
   const T onf = on ? (T)1 : (T)0;
   const T dqx = onf * dppx<0x00>(d_me), dqy = onf * dppx<0x55>(d_me), dqz = onf * dppx<0xAA>(d_me);   // my foot's lever arm, zero for a swing foot
   // (kernel-uniform weights pass through an empty asm so that products of two of them are not hoisted out of the tile / horizon loop and held
@@ -246,7 +192,6 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   };
 
   if constexpr (!CONS_EARLY) WBC_QP_FORM_ROWS;
-#undef WBC_QP_FORM_ROWS
   // per-lane state of the active set: row c3 of P_k, slot c3 of foot k (N^+ row, multiplier, constraint id), |active set of foot k|
   T Pr0 = c3 == 0 ? (T)1 : (T)0, Pr1 = c3 == 1 ? (T)1 : (T)0, Pr2 = c3 == 2 ? (T)1 : (T)0;
   T Np0 = 0, Np1 = 0, Np2 = 0, u_s = 0;
@@ -481,9 +426,6 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   const long long st_t1 = __builtin_readcyclecounter();
   long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long st_last = st_t1;
-#define SEG(i) do { const long long now_ = __builtin_readcyclecounter(); seg[i] += now_ - st_last; st_last = now_; } while (0)
-#else
-#define SEG(i) do {} while (0)
 #endif
 #pragma clang loop unroll(disable)
   for (int ph = 0; ph < (SPEC ? 2 : 1); ++ph) {   // (SPEC: the iteration on b~, then -- from the point moved to b -- whatever is left of it; rolled: one copy of the loop)
@@ -783,7 +725,7 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
         const int hslot = 16 * f + (int)((tx >> 4) & 15);   // (my state's slot in the workgroup)
         jl0 = (T)hand_img[(24 + c3) * 64 + hslot]; jl1 = (T)hand_img[(27 + c3) * 64 + hslot]; jl2 = (T)hand_img[(30 + c3) * 64 + hslot];
       } else if (geom_jc) {
-        jl0 = GLD(a.Jc, (3 * f + 0) * 18 + 6 + jm); jl1 = GLD(a.Jc, (3 * f + 1) * 18 + 6 + jm); jl2 = GLD(a.Jc, (3 * f + 2) * 18 + 6 + jm);
+        jl0 = GLD(a.Jc, JC_LEG_WORD(f, 0, jm)); jl1 = GLD(a.Jc, JC_LEG_WORD(f, 1, jm)); jl2 = GLD(a.Jc, JC_LEG_WORD(f, 2, jm));
       } else {
         jl0 = WSLD(WS_JCL + 9 * f + 0 + c3); jl1 = WSLD(WS_JCL + 9 * f + 3 + c3); jl2 = WSLD(WS_JCL + 9 * f + 6 + c3);
       }
@@ -811,39 +753,21 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
       if (l16 == 0) { who.iimg[who.tile + stg_slot] = status; who.iimg[2 * who.tile + stg_slot] = iter; }
     } else if (l16 == 0 && to_mem) {
       a.status[s32] = status;
-#ifdef WBC_QP_STAMP
-      {
-        const long long vals[8] = {st_t1 - st_t0, seg[0], seg[1], seg[2], seg[3], seg[4], seg[5], seg[6]};
-        long long lo = vals[0], hi = vals[1];
-        if (grp == 1) { lo = vals[2]; hi = vals[3]; } else if (grp == 2) { lo = vals[4]; hi = vals[5]; } else if (grp == 3) { lo = vals[6]; hi = vals[7]; }
-        lo >>= 4; hi >>= 4;
-        if (lo > 0xFFFF) lo = 0xFFFF;
-        if (hi > 0x7FFF) hi = 0x7FFF;
-        if (a.iters) a.iters[s32] = (int)(lo | (hi << 16));
-      }
-#else
-      if (a.iters) a.iters[s32] = iter;
-#endif
+      GST_ITERS(iter);
     }
   }
   WBC_QSTAMP(11);
-#undef SEG
 #undef IMG
-#undef GST
 #undef WSLD
 #undef BLD
-#undef GLD
 }
 
-// the QP body of a scalar type.  WBC_QP_STRUCT = 2 (default): the structured form for both scalar types (fp32 solvers: fp32 arrays,
-// fp64 arithmetic); 1: structured for fp64, the orthogonal-factor form (qp_group16.hip.hpp) for fp32; 0: always the latter
+// the QP body of a scalar type: the structured form for both (fp32 solvers: fp32 arrays, fp64 arithmetic).  A plain forwarding name, kept because the
+// kernels' device code is not the same when they name qp_struct16_body themselves (docs/DESIGN_HISTORY.md)
 template <class T, bool WSLDS, bool RHAT = false, int SPW = 16, bool TILED = false, int WPB = (WSLDS || TILED) ? 4 : 1, class Idle = QpNoIdle, bool PRE = false, int WARM = 0, int STG = 0>
 WBC_DEV void qp_body(const DevParams<T>& prm, const QpArgs<T>& a, const QpJidx& jmap, const T* wsl, const QpSync* sync = nullptr,
                      const QpWho who = QpWho{0, false}, Idle idle = Idle(), int* carry = nullptr) {
-  static_assert(STG == 0 || true, "staged tiles run the structured body");
-  if constexpr (WARM != 0 || ((true || std::is_same<T, double>::value)))
-    qp_struct16_body<T, WSLDS, RHAT, SPW, TILED, WPB, Idle, PRE, WARM, STG>(prm, a, jmap, wsl, sync, who, idle, carry);
-  else qp_group16_body<T, WSLDS, RHAT, SPW, TILED, WPB, Idle>(prm, a, jmap, wsl, sync, who, idle);
+  qp_struct16_body<T, WSLDS, RHAT, SPW, TILED, WPB, Idle, PRE, WARM, STG>(prm, a, jmap, wsl, sync, who, idle, carry);
 }
 
 }  // namespace wbc

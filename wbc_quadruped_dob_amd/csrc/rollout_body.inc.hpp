@@ -49,7 +49,7 @@
   // stores drain until barrier B) and phase 2 reading them there instead of through L2.  Measured (profiles/r05f_ab_rollout_reslds_*.log, us per tick at
   // 1 024 robots, off -> on): fp32 10.57 -> 10.01, fp64 12.51 -> 12.80 (128 robots 12.30 -> 12.67, planner in the loop 15.15 -> 15.6) -- round 4 had seen the
   // same sign for fp64.  1 (default): fp32 kernels only; 0: never; 2: both scalar types (A/B)
-  constexpr bool RES_LDS = true || (sizeof(T) == 4);
+  constexpr bool RES_LDS = true;
   __shared__ T fact_sh[true ? INT_FACT_WORDS * 64 : 1];   // the integrator's phase 1 -> phase 2 hand-over (integrate.hip.hpp, PHASE)
   __shared__ T st_sh[SIMG_WORDS * 16];             // the workgroup's states
   __shared__ T ref_sh[(TRACK) ? 24 * 16 : 1];         // (planner in the loop) this tick's references: planner role -> rnea role
