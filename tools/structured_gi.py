@@ -136,6 +136,7 @@ class StructuredGI:
             order = [c for k in range(4) for c in act[k]]
         eps = np.finfo(float).eps
         Rnorm, it, status = 1.0, 0, 0
+        self.trace = []     # one letter per trip: A full step (the candidate is added), P partial step + drop, D dual-only step + drop
         slack = lambda c, xx: self.C[c].dot(xx[3 * (c // 6):3 * (c // 6) + 3]) - self.rhs[c]
 
         def refresh(k):
@@ -215,6 +216,7 @@ class StructuredGI:
                         u[c] -= t1 * r[c]
                     up += t1
                     Ginv = drop(l, Ginv)
+                    self.trace.append("D")
                     continue
                 full = not (t1 < t2)
                 t = t2 if full else t1
@@ -225,6 +227,7 @@ class StructuredGI:
                 if not full:
                     Ginv = drop(l, Ginv)
                     sip = slack(ip, x)
+                    self.trace.append("P")
                     continue
                 act[kp].append(ip); order.append(ip); u[ip] = up
                 refresh(kp)
@@ -234,6 +237,7 @@ class StructuredGI:
                 else:
                     Ginv = np.linalg.inv(self.G(P))
                 Rnorm = max(Rnorm, np.sqrt(zn))
+                self.trace.append("A")
                 break
         return x, it, status, u
 

@@ -61,6 +61,8 @@ template <class T, bool OBSERVER, bool MATS, bool WARM = false> constexpr bool f
 template <class T, bool MATS, bool WARM> constexpr int fused_store() { return (MATS && !WARM && sizeof(T) == 8) ? ST_WT : ST_PLAIN; }
 // The QP wavefronts' own stores -- tau, f, status, iters, the active set: the tick's LAST stores -- keep plain stores: write-through there gave +1.5 % at 4 096 fp64
 // states, 2.4 times the parent's run-to-run spread and so short of the gain rule on its own, and cost the observer-on tick 1 % (docs/DESIGN_HISTORY.md).
+// The QP trips of the cold fp64 observer-off tick branch around the search and the add-commit that no live row of the wavefront needs (qp_struct16.hip.hpp, SKIP).
+template <class T, bool OBSERVER, bool WARM> constexpr bool fused_trip_skip() { return !OBSERVER && !WARM && sizeof(T) == 8; }
 template <class T, bool OBSERVER, bool MATS, bool WARM = false> constexpr int fused_threads() { return OBSERVER ? 384 + 64 * FUSED_OBS_WAVES : (fused_split_h<T, OBSERVER, MATS, WARM>() ? 448 : 384); }
 // WARM: the QP of every state starts from the active set in qa.aset_in (wbc_step_batch_warm: dependent ticks of a closed loop)
 // LEAD (observer off: the nine types launch_fused_tick names, k_fused.hip; observer on: empty): leading arguments, ordered by first use, for what the wavefronts need in front of their
@@ -153,9 +155,9 @@ __global__ __launch_bounds__((fused_threads<T, OBSERVER, MATS, WARM>()), 1) void
       const int* const zs = zidx_s;
       const unsigned tq = threadIdx.x;
       auto idle = [=] __device__() { if (!a.skip_consts) structural_consts_quarter<T, fused_store<T, MATS, WARM>()>(model, a, zs, tq); };
-      qp_body<T, true, OBSERVER, 16, false, 4, decltype(idle), false, WARM ? 1 : 0>(prm, qa, jmap, wsl, &sy, QpWho{0, false}, idle);
+      qp_body<T, true, OBSERVER, 16, false, 4, decltype(idle), false, WARM ? 1 : 0, 0, fused_trip_skip<T, OBSERVER, WARM>()>(prm, qa, jmap, wsl, &sy, QpWho{0, false}, idle);
     } else
-    qp_body<T, true, OBSERVER, 16, false, 4, QpNoIdle, false, WARM ? 1 : 0>(prm, qa, jmap, wsl, &sy);
+    qp_body<T, true, OBSERVER, 16, false, 4, QpNoIdle, false, WARM ? 1 : 0, 0, fused_trip_skip<T, OBSERVER, WARM>()>(prm, qa, jmap, wsl, &sy);
   }
 }
 

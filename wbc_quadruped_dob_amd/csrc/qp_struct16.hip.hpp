@@ -82,7 +82,7 @@ WBC_DEV void s16_cold_inverse_row(int mask, T d_me, T alpha_l, T s0, T s1, T s2,
 // A set with more than three rows on a foot, dependent rows or a negative multiplier is no S-pair of the dual method: that row of the
 // wavefront repeats the set-up with the empty set (= the cold start; the loop below runs at most twice).  The QP is strictly convex, so
 // the start changes the iteration count, never the solution.
-template <class TS, bool WSLDS, bool RHAT = false, int SPW = 16, bool TILED = false, int WPB = (WSLDS || TILED) ? 4 : 1, class Idle = QpNoIdle, bool PRE = false, int WARM = 0, int STG = 0>
+template <class TS, bool WSLDS, bool RHAT = false, int SPW = 16, bool TILED = false, int WPB = (WSLDS || TILED) ? 4 : 1, class Idle = QpNoIdle, bool PRE = false, int WARM = 0, int STG = 0, bool SKIP = false>
 WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, const QpJidx& jmap, const TS* wsl, const QpSync* sync = nullptr,
                               const QpWho who = QpWho{0, false}, Idle idle = Idle(), int* carry = nullptr) {
   using T = double;
@@ -100,6 +100,7 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   // strictly convex, so f, tau, status do not depend on b~ at all -- a torn or already updated read of r_prev only makes the guess better or worse.
   constexpr bool SPEC = WSLDS && RHAT && WARM == 0 && !PRE && !TILED;
   static_assert(!(WARM != 0 && PRE), "warm starts set their blocks up themselves");
+  static_assert(!SKIP || (WARM == 0 && !SPEC && !PRE && STG == 0), "SKIP leaves a finished row's factors stale: only where nothing reads them behind the loop");
   WBC_QP_ROW_PROLOGUE
   S16Lds<T>* Lp;
   if constexpr (STG != 0) Lp = (S16Lds<T>*)who.tab;     // (staged tiles: this wavefront's tables live in the kernel's dynamic LDS, beside the image)
@@ -416,6 +417,12 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   // independent chains of a trip sit side by side -- the ratio test over the active multipliers, and the full step with the
   // search for the NEXT candidate at its end point, which is speculative: it is used when the step turns out to be full
   // (almost always) -- and per-row decisions are committed by selects at the end.
+  // One exception (SKIP, the cold fp64 observer-off one-launch tick): the add-commit -- the rank-one update of G_A^-1, the new row of N^+, the
+  // downdate of P and its LDS copy -- sits behind a wave-uniform branch and runs only when some row of the wavefront adds its candidate AND has a
+  // next one.  Every row ends on such an add, and the wavefronts that end the tick have one live row left, so their last trip no longer issues
+  // ~70 instructions whose results nothing reads: a trip is bound by the issue rate of a lone wavefront, not by latency.  The forms that read
+  // the factors or the multipliers behind the loop (WARM, SPEC, PRE, STG) keep SKIP off.  The same branch around the search of a trip on which
+  // no row takes its full step was measured and not kept: it puts the ratio test in front of the search on every trip (docs/DESIGN_HISTORY.md).
   int ip = -1, status = 0, iter = 0;
   int iter0 = 0;   // (SPEC) trips of the phase on b~: the second phase has the whole of max_iter (it used to get what phase 0 left)
   bool done = !live;
@@ -531,7 +538,9 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
     u_s = (addg && slot_act) ? u_s - t2 * r_me : u_s;
     u_c = addg ? u_c + t2 : u_c;
     // full step: the candidate joins the active set of its foot
-    {
+    // (SKIP: only when some row of the wavefront goes on from the enlarged set.  A row that adds and finds no next candidate is finished, and what the
+    //  commit would leave -- G_A^-1, N^+, P and its LDS copy, the slot's multiplier and id, Rn2 -- is read by later trips of that row only)
+    if (!SKIP || __ballot(addg && nfound) != 0ull) {
       const T gy = addg ? yi * (rz * ralpha) : (T)0;                 // y_i / (alpha z . n+)
       sfor<0, 6>([&](auto jc) __attribute__((always_inline)) { constexpr int j = decltype(jc)::value; Gr[j] += gy * y[j]; });
       const T ivv = rcp_nr1(vv > 0 ? vv : (T)1);
@@ -549,6 +558,8 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
       qk += upd ? 1 : 0;
       prow[0] = Pr0; prow[1] = Pr1; prow[2] = Pr2;                 // every lane, every trip: its (possibly unchanged) row
       Rn2 = (addg && zn > Rn2) ? zn : Rn2;
+    }
+    {   // what the outputs and the loop's own control read: every trip
       actA = actA || (addg && own && !(ipc & 1));
       actB = actB || (addg && own && (ipc & 1));
       // the next candidate of the rows that added: the speculative search was made at their new point
@@ -764,10 +775,10 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
 
 // the QP body of a scalar type: the structured form for both (fp32 solvers: fp32 arrays, fp64 arithmetic).  A plain forwarding name, kept because the
 // kernels' device code is not the same when they name qp_struct16_body themselves (docs/DESIGN_HISTORY.md)
-template <class T, bool WSLDS, bool RHAT = false, int SPW = 16, bool TILED = false, int WPB = (WSLDS || TILED) ? 4 : 1, class Idle = QpNoIdle, bool PRE = false, int WARM = 0, int STG = 0>
+template <class T, bool WSLDS, bool RHAT = false, int SPW = 16, bool TILED = false, int WPB = (WSLDS || TILED) ? 4 : 1, class Idle = QpNoIdle, bool PRE = false, int WARM = 0, int STG = 0, bool SKIP = false>
 WBC_DEV void qp_body(const DevParams<T>& prm, const QpArgs<T>& a, const QpJidx& jmap, const T* wsl, const QpSync* sync = nullptr,
                      const QpWho who = QpWho{0, false}, Idle idle = Idle(), int* carry = nullptr) {
-  qp_struct16_body<T, WSLDS, RHAT, SPW, TILED, WPB, Idle, PRE, WARM, STG>(prm, a, jmap, wsl, sync, who, idle, carry);
+  qp_struct16_body<T, WSLDS, RHAT, SPW, TILED, WPB, Idle, PRE, WARM, STG, SKIP>(prm, a, jmap, wsl, sync, who, idle, carry);
 }
 
 }  // namespace wbc
