@@ -231,6 +231,31 @@ class QuadrupedWBC {
           "wbc_integrate_ground_stick_batch");
   }
 
+  // Terrain heightfield (wbc_hip.h, "Terrain heightfield"): the planes under the feet and the footholds' heights from a map, for callers that run the
+  // batch calls on solver()'s device buffers.  The wbc_terrain's z and tile are DEVICE pointers, so there is no single-robot host-pointer form.
+  // gaitTerrain / gaitEstimatedTerrain are wbc_gait_batch / wbc_gait_estimated_batch followed by terrainFeet on the mask and swing they leave, one launch
+  // each; the same normals and height buffers then go to the step and to integrateGround[Stick].  (The argument order of the C calls.)
+  void terrainSample(const wbc_terrain& t, size_t M, const void* xy, void* z, void* n, void* d, void* stream = nullptr) {
+    check(wbc_terrain_sample_batch(solver_, &t, M, xy, z, n, d, stream), "wbc_terrain_sample_batch");
+  }
+  void terrainFeet(const wbc_terrain& t, size_t N, const void* q, const int* mask /* with swing, or both nullptr */, void* swing, void* normals,
+                   void* height, void* surf = nullptr, void* stream = nullptr) {
+    check(wbc_terrain_feet_batch(solver_, &t, N, q, mask, swing, normals, height, surf, stream), "wbc_terrain_feet_batch");
+  }
+  void gaitTerrain(size_t N, const void* q, const void* v, const void* cmd, const int* contact /* may be nullptr */, void* phase, int* mask,
+                   void* swing, int* events /* may be nullptr */, const wbc_terrain& t, void* normals, void* height, void* surf = nullptr,
+                   void* stream = nullptr) {
+    check(wbc_gait_terrain_batch(solver_, N, q, v, cmd, contact, phase, mask, swing, events, &t, normals, height, surf, stream),
+          "wbc_gait_terrain_batch");
+  }
+  void gaitEstimatedTerrain(size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r, const void* f_prev,
+                            void* normals /* in/out */, int* contact, void* phase, int* mask, void* swing, int* events /* may be nullptr */,
+                            void* f_est /* may be nullptr */, const wbc_terrain& t, void* height, void* surf = nullptr, void* stream = nullptr) {
+    check(wbc_gait_estimated_terrain_batch(solver_, N, q, v, cmd, Jc, r, f_prev, normals, contact, phase, mask, swing, events, f_est, &t, height, surf,
+                                           stream),
+          "wbc_gait_estimated_terrain_batch");
+  }
+
   // Joint torque limits (wbc_hip.h, "Joint torque limits behind a tick").  effortLimits(): the URDF's <limit effort> per joint in jointNames() order,
   // HUGE_VAL where it gives none.  setTorqueLimits(): the limits the post-pass enforces (one value > 0 per joint; empty = back to the URDF's).
   std::vector<double> effortLimits() const {

@@ -514,8 +514,9 @@ int wbc_compute_swing_reference(wbc_solver* s, const double* q, const double* v,
  * rounding, because the compiler may contract their products.
  * Stream rules as for wbc_swing_reference_batch: no allocation, no synchronisation, hipGraph-capturable; phase, mask and swing advance IN PLACE; N == 0
  * returns WBC_OK without looking at the buffers; a NULL required pointer: WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
- * Out of scope: the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown (the schedule says stance and no contact is sensed); terrain-normal
- * footholds; fusing this call into the fused reference + swing kernel, whose fp64 instantiation already uses 256 VGPRs and would spill. */
+ * Out of scope: the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown (the schedule says stance and no contact is sensed); fusing this
+ * call into the fused reference + swing kernel, whose fp64 instantiation already uses 256 VGPRs and would spill.  (Footholds and foot
+ * planes on a mapped terrain: wbc_gait_terrain_batch, "Terrain heightfield" below.) */
 #define WBC_GAIT_CMD_WORDS 4
 typedef struct wbc_gait_params {
   size_t struct_size;   /* sizeof(wbc_gait_params) of the caller's build */
@@ -577,8 +578,8 @@ int wbc_compute_gait(wbc_solver* s, const double* q, const double* v, const doub
  * wbc_integrate_ground_stick_batch ("Stiction" below) add a per-foot anchor spring that holds it.
  * Stream rules as for wbc_gait_batch: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at the buffers; a NULL
  * required pointer: WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
- * Out of scope: the payload plant (wbc_integrate_plant_batch); the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown in the gait rule;
- * terrain-normal footholds.  (Stiction: the calls of the next section.) */
+ * Out of scope: the payload plant (wbc_integrate_plant_batch); the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown in the gait rule.
+ * (Stiction: the calls of the next section.  normals and height from a map: "Terrain heightfield" below.) */
 typedef struct wbc_ground_params {
   size_t struct_size;     /* sizeof(wbc_ground_params) of the caller's build */
   double k_n, c_n, c_t;   /* N/m, N s/m, N s/m; all >= 0 and finite */
@@ -627,8 +628,8 @@ int wbc_integrate_ground_batch(wbc_solver* s, size_t N, void* q, void* v, const 
  * tests/test_stick_oracle.py holds the measured figures, a and b among them.  A caller with another dt or a lighter leg scales k_t with m_eff / dt^2.
  * Stream rules as for the ground calls: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at the buffers; a
  * NULL required pointer (anchor and stick included): WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
- * Out of scope: the payload plant (wbc_integrate_plant_batch); the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown in the gait rule;
- * terrain-normal footholds. */
+ * Out of scope: the payload plant (wbc_integrate_plant_batch); the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown in the gait rule.
+ * (normals and height from a map: "Terrain heightfield" below.) */
 typedef struct wbc_stiction_params {
   size_t struct_size;     /* sizeof(wbc_stiction_params) of the caller's build */
   double k_t;             /* N/m, >= 0 and finite */
@@ -688,7 +689,7 @@ int wbc_integrate_ground_stick_batch(wbc_solver* s, size_t N, void* q, void* v, 
  * Stream rules as for the ground calls: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at the buffers; a
  * NULL required pointer (contact included): WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY.
  * Out of scope: the base rows of r; a contact observer of its own; the rollout kernels and wbc_rollout_*; wbc_multi_*; the payload plant; late
- * touchdown in the gait rule; terrain-normal footholds. */
+ * touchdown in the gait rule.  (The same call on a mapped terrain: wbc_gait_estimated_terrain_batch, "Terrain heightfield" below.) */
 typedef struct wbc_contact_params {
   size_t struct_size;     /* sizeof(wbc_contact_params) of the caller's build */
   double f_on, f_off;     /* N; >= 0 and finite, f_off <= f_on */
@@ -708,6 +709,78 @@ int wbc_gait_estimated_batch(wbc_solver* s, size_t N, const void* q, const void*
  * the optional f_est[12], fn_est[4], singular[1] out).  Synchronises. */
 int wbc_compute_contact_estimate(wbc_solver* s, const double* Jc, const double* r, const double* f_prev, const double* normals, int* contact,
                                  double* f_est, double* fn_est, int* singular);
+
+/* Terrain heightfield: per-foot planes and foothold heights on the device.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct, call or
+ * default changes; detect it by these symbols).  The step, the contact estimate and the ground calls take one plane per foot (normals [12][N],
+ * height [4][N]) as caller buffers, and wbc_gait_batch puts every foothold at the single height cmd row 3.  These calls write those planes and the
+ * footholds' heights from a map, so that a foot that moves meets other ground with no host work between launches.  The map: n_tiles regular grids of
+ * node heights, one tile per state.  All buffers are caller-owned DEVICE memory like every batch array; the struct is read on the host at call time and
+ * its scalars travel as kernel arguments: nothing is uploaded, allocated or synchronised, and every call is hipGraph-capturable (a captured graph keeps
+ * the values it was captured with).
+ * The host forms, in double, rounded to the solver's scalar type T and passed in:  x0, y0,  inv_cell = 1 / cell,  x_max = x0 + (nx - 1) cell,
+ * y_max = y0 + (ny - 1) cell.  The law for a point (x, y) on tile t, in T, in this operation order:
+ *   xc = min(max(x, x0), x_max)            yc likewise        (a point off the grid sees the tangent plane at the nearest edge point)
+ *   gx = (xc - x0) inv_cell                ix = min((int)gx, nx - 2)     u = gx - ix        (gy, iy, w likewise)
+ *   z00, z10, z01, z11 = nodes (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) of tile t
+ *   a = z00 + u (z10 - z00)    b = z01 + u (z11 - z01)
+ *   zs = a + w (b - a)
+ *   zx = ((z10 - z00) + w ((z11 - z01) - (z10 - z00))) inv_cell         zy = (b - a) inv_cell
+ *   n  = (-zx, -zy, 1) rsqrt(zx^2 + zy^2 + 1)                            (1 / sqrt, as the kernels normalise today)
+ *   d  = n.x xc + n.y yc + n.z zs
+ * zs is continuous.  n (and with it d) is piecewise: it is the normal of the cell's bilinear patch and JUMPS at cell edges.  Non-finite x, y are the
+ * caller's promise, as for q; so are tile values outside [0, n_tiles).  The compiler may contract the products, so the outputs are exact only to
+ * rounding -- except where u and w are exactly 0 or 1 (a point on a node of a dyadic grid): there every product in zs is exact, zs is that of the
+ * same arithmetic on a CPU bit for bit, and with u = w = 0 (every node but the last row's and column's) zs is the node's own bits.
+ *   wbc_terrain_sample_batch   the law at M <= max_batch caller-given points xy [2][M] (row 0 x, row 1 y; terrain->tile is then [M] or NULL):
+ *                              z [M], n [3][M], d [M], each may be NULL -- for planners and tests.
+ *   wbc_terrain_feet_batch     per state and foot k, p_f(q) from the leg's position chain (the arithmetic wbc_gait_batch latches p0 with; joint orders
+ *                              that are not leg-major work), then the law at p_f,xy:  rows 3k .. 3k+2 of normals = n,  height[k] = d,  surf[k] = zs
+ *                              (surf [4][N] may be NULL).  These are the planes wbc_step_batch, the contact estimate and the ground calls read.
+ *                              mask and swing are given both or neither.  Given: for every foot whose bit of mask is CLEAR, swing word 9k+5 (p1_z) :=
+ *                              zs at that plan's own (p1_x, p1_y) = words 9k+3, 9k+4.  No other swing word is touched, and feet with a set bit are
+ *                              untouched bit for bit.  The rule is idempotent, so it is the same for retarget 0 and 1.
+ *   wbc_gait_terrain_batch     wbc_gait_batch's arguments + terrain, normals, height, surf: ONE launch whose outputs are those of wbc_gait_batch followed
+ *                              by wbc_terrain_feet_batch(mask, swing = what the gait call left).  cmd row 3 is then dead for lifted feet.
+ *   wbc_gait_estimated_terrain_batch   the same behind wbc_gait_estimated_batch.  normals is IN/OUT: the contact law reads the previous tick's
+ *                              planes, then they are overwritten with this tick's (before the first tick the caller stores any unit normals).
+ * The walking tick stays at four launches with no host work between them:
+ *   gait[_estimated]_terrain -> reference_swing -> step -> integrate_ground[_stick]
+ * with ONE normals and ONE height buffer through all four.
+ * Why: on the CPU restatement of the loop (tests/terrain_ref.py; 4 robots, 512 ticks of 2^-10 s, the stiction plant, 4 tiles of 64 x 48 nodes, cell
+ * 2^-6, a 0.05 ramp with a 6 mm ripple) the gap p_f,z - zs(p_f,xy) of a foot at the tick of its touchdown event stays within 0.80 mm of the
+ * surface when p1_z and the normals come from the map, as on flat ground (0.61 mm), and reaches 14.9 mm when p1_z = z_g and the
+ * controller's normals are e_z -- the foot is declared down while still in the air.  Every QP status is 0 in all three loops.  tests/test_terrain_oracle.py holds the measured figures.  With
+ * footholds read from the map, late touchdown in the gait rule is not needed for mapped terrain.
+ * A bad struct gives WBC_E_INVALID: nx or ny < 2, n_tiles < 1, a non-finite x0, y0 or cell, cell <= 0, a NULL z, a wrong struct_size, or
+ * n_tiles ny nx >= 2^28 nodes (every node is reached by a 32-bit byte offset).
+ * Stream rules as for the gait calls: N == 0 (M == 0) returns WBC_OK without looking at anything; a NULL required pointer (terrain included; mask
+ * without swing or swing without mask): WBC_E_INVALID; then the struct's own checks; N > max_batch: WBC_E_CAPACITY -- all before the device is touched.
+ * There is no single-robot host-pointer form: the grid would have to be uploaded inside the call.
+ * Out of scope: the rollout kernels and wbc_rollout_*; wbc_multi_*; the payload plant; late touchdown in the gait rule; choosing footholds by terrain
+ * quality (avoiding edges and slopes); smoothed (C1) normals; terrain sensing or estimation: the map is given. */
+typedef struct wbc_terrain {
+  size_t struct_size; /* sizeof(wbc_terrain) of the caller's build */
+  int nx, ny;         /* nodes per row, rows; each >= 2 */
+  int n_tiles;        /* >= 1 */
+  double x0, y0;      /* world x, y of node (0, 0); finite */
+  double cell;        /* node spacing, m; > 0, finite */
+  const void* z;      /* DEVICE, solver scalar type, [n_tiles][ny][nx]: z[(t ny + iy) nx + ix] = height at (x0 + ix cell, y0 + iy cell) */
+  const int* tile;    /* DEVICE [N] (or [M]) or NULL = tile 0 for every state; values in [0, n_tiles) are the caller's promise */
+} wbc_terrain;
+int wbc_terrain_sample_batch(wbc_solver* s, const wbc_terrain* terrain, size_t M, const void* xy, void* z /* may be NULL */, void* n /* may be NULL */,
+                             void* d /* may be NULL */, void* stream);
+int wbc_terrain_feet_batch(wbc_solver* s, const wbc_terrain* terrain, size_t N, const void* q, const int* mask /* may be NULL */,
+                           void* swing /* in/out [36][N]; NULL with mask */, void* normals /* out [12][N] */, void* height /* out [4][N] */,
+                           void* surf /* may be NULL, [4][N] */, void* stream);
+int wbc_gait_terrain_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact /* may be NULL */,
+                           void* phase /* in/out [N] */, int* mask /* in/out [N] */, void* swing /* in/out [36][N] */, int* events /* may be NULL, [N] */,
+                           const wbc_terrain* terrain, void* normals /* out [12][N] */, void* height /* out [4][N] */, void* surf /* may be NULL */,
+                           void* stream);
+int wbc_gait_estimated_terrain_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r,
+                                     const void* f_prev, void* normals /* in/out [12][N] */, int* contact /* in/out [N] */, void* phase /* in/out [N] */,
+                                     int* mask /* in/out [N] */, void* swing /* in/out [36][N] */, int* events /* may be NULL, [N] */,
+                                     void* f_est /* may be NULL */, const wbc_terrain* terrain, void* height /* out [4][N] */,
+                                     void* surf /* may be NULL */, void* stream);
 
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and

@@ -286,6 +286,12 @@ def lib():
             L.wbc_contact_estimate_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
             L.wbc_gait_estimated_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 14
             L.wbc_compute_contact_estimate.argtypes = [C.c_void_p] * 9
+        # terrain heightfield: additive to ABI 10, detected by the symbols in the same way (_terrain_lib)
+        if hasattr(L, "wbc_gait_terrain_batch"):
+            L.wbc_terrain_sample_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
+            L.wbc_terrain_feet_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
+            L.wbc_gait_terrain_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 13
+            L.wbc_gait_estimated_terrain_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 17
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -352,6 +358,14 @@ def _contact_lib():
     L = lib()
     if not hasattr(L, "wbc_gait_estimated_batch"):
         raise RuntimeError("%s lacks the contact-estimate entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+def _terrain_lib():
+    """lib(), for the terrain calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_gait_terrain_batch"):
+        raise RuntimeError("%s lacks the terrain entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     return L
 
 
@@ -502,6 +516,32 @@ class ContactParams(C.Structure):
 
     def as_dict(self):
         return dict(f_on=self.f_on, f_off=self.f_off, det_min=self.det_min)
+
+
+class TerrainStruct(C.Structure):
+    """wbc_terrain (include/wbc_hip.h, "Terrain heightfield")"""
+    _fields_ = [("struct_size", C.c_size_t), ("nx", C.c_int), ("ny", C.c_int), ("n_tiles", C.c_int), ("x0", C.c_double), ("y0", C.c_double),
+                ("cell", C.c_double), ("z", C.c_void_p), ("tile", C.c_void_p)]
+
+
+class Terrain:
+    """A heightfield for the terrain calls: z [n_tiles, ny, nx] (or [ny, nx] = one tile), a contiguous CUDA tensor of the solver's scalar type, node
+    (ix, iy) of a tile at (x0 + ix cell, y0 + iy cell); tile: int32 CUDA tensor, one entry per state (or per sample point), or None = tile 0.  Holds the
+    C struct and keeps both tensors alive; the library checks the values at every call (WbcError)."""
+
+    def __init__(self, z, x0, y0, cell, tile=None):
+        if z.dim() == 2:
+            z = z.unsqueeze(0)
+        assert z.dim() == 3 and z.is_cuda and z.is_contiguous(), "z: a contiguous CUDA tensor [n_tiles, ny, nx]"
+        if tile is not None:
+            assert tile.is_cuda and tile.is_contiguous() and str(tile.dtype) == "torch.int32", "tile: a contiguous int32 CUDA tensor"
+        self.z, self.tile = z, tile
+        self.c = TerrainStruct(C.sizeof(TerrainStruct), z.shape[2], z.shape[1], z.shape[0], float(x0), float(y0), float(cell), z.data_ptr(),
+                               tile.data_ptr() if tile is not None else None)
+
+    def with_tile(self, tile):
+        """the same grid with another per-state tile tensor"""
+        return Terrain(self.z, self.c.x0, self.c.y0, self.c.cell, tile)
 
 
 GAIT_CMD_WORDS = 4   # include/wbc_hip.h: WBC_GAIT_CMD_WORDS -- cmd [GAIT_CMD_WORDS, N]: vx, vy (heading frame), wz, z_g
@@ -1188,6 +1228,84 @@ class Solver:
                                                        self._ptr(mask, 1, N, i32), self._ptr(swing, SWING_WORDS, N), self._ptr(events, 1, N, i32),
                                                        self._ptr(f_est, 3 * m.nf, N), self._stream()), "wbc_gait_estimated_batch")
         return dict(contact=contact, phase=phase, mask=mask, swing=swing, events=events, f_est=f_est)
+
+    def _terrain_arg(self, terrain, n):
+        assert terrain.z.dtype == self.tdtype, (terrain.z.dtype, self.tdtype)
+        assert terrain.tile is None or terrain.tile.numel() == n, (tuple(terrain.tile.shape), n)
+        return C.byref(terrain.c)
+
+    def _terrain_out(self, N, normals, height, surf, want_surf):
+        m = self.model
+        normals = self.empty(3 * m.nf, N) if normals is None else normals
+        height = self.empty(m.nf, N) if height is None else height
+        if surf is None and want_surf:
+            surf = self.empty(m.nf, N)
+        return normals, height, surf
+
+    def terrain_sample(self, terrain, xy, z=None, n=None, d=None, want_z=True, want_n=True, want_d=True):
+        """The sampling law at the points xy [2, M] (wbc_terrain_sample_batch): the surface height z [M], the unit normal n [3, M] of the cell's
+        bilinear patch and the offset d [M] of the tangent plane n . x = d.  terrain.tile, if any, has M entries.  want_* allocates an output that was
+        not passed; an output neither passed nor wanted is not computed.  Returns dict(z, n, d)."""
+        M = xy.shape[1]
+        if z is None and want_z:
+            z = self.empty(1, M).view(M)
+        if n is None and want_n:
+            n = self.empty(3, M)
+        if d is None and want_d:
+            d = self.empty(1, M).view(M)
+        _check(_terrain_lib().wbc_terrain_sample_batch(self._h, self._terrain_arg(terrain, M), M, self._ptr(xy, 2, M), self._ptr(z, 1, M),
+                                                       self._ptr(n, 3, M), self._ptr(d, 1, M), self._stream()), "wbc_terrain_sample_batch")
+        return dict(z=z, n=n, d=d)
+
+    def terrain_feet(self, terrain, q, mask=None, swing=None, normals=None, height=None, surf=None, want_surf=False):
+        """The terrain's planes under the four feet of every state (wbc_terrain_feet_batch): normals [12, N] and height [4, N] as the step, the contact
+        estimate and the ground calls read them, surf [4, N] = the surface height under each foot.  mask (int32 [N]) and swing [SWING_WORDS, N] are
+        given both or neither: p1_z of every foot whose bit is clear becomes the surface height at its plan's own p1_x, p1_y, IN PLACE.  Returns
+        dict(normals, height, surf, swing)."""
+        m = self.model
+        N = q.shape[1]
+        normals, height, surf = self._terrain_out(N, normals, height, surf, want_surf)
+        _check(_terrain_lib().wbc_terrain_feet_batch(self._h, self._terrain_arg(terrain, N), N, self._ptr(q, m.nq, N),
+                                                     self._ptr(mask, 1, N, self.torch.int32), self._ptr(swing, SWING_WORDS, N),
+                                                     self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(surf, m.nf, N),
+                                                     self._stream()), "wbc_terrain_feet_batch")
+        return dict(normals=normals, height=height, surf=surf, swing=swing)
+
+    def gait_terrain(self, terrain, q, v, cmd, phase, mask, swing, contact=None, events=None, normals=None, height=None, surf=None, want_surf=False):
+        """gait() followed by terrain_feet(mask, swing = what it left), as one launch (wbc_gait_terrain_batch).  Returns dict(phase, mask, swing,
+        events, normals, height, surf)."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        normals, height, surf = self._terrain_out(N, normals, height, surf, want_surf)
+        _check(_terrain_lib().wbc_gait_terrain_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(cmd, GAIT_CMD_WORDS, N),
+                                                     self._ptr(contact, 1, N, i32), self._ptr(phase, 1, N), self._ptr(mask, 1, N, i32),
+                                                     self._ptr(swing, SWING_WORDS, N), self._ptr(events, 1, N, i32), self._terrain_arg(terrain, N),
+                                                     self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(surf, m.nf, N),
+                                                     self._stream()), "wbc_gait_terrain_batch")
+        return dict(phase=phase, mask=mask, swing=swing, events=events, normals=normals, height=height, surf=surf)
+
+    def gait_estimated_terrain(self, terrain, q, v, cmd, Jc, r, f_prev, normals, contact, phase, mask, swing, events=None, f_est=None, want_f=False,
+                               height=None, surf=None, want_surf=False):
+        """gait_estimated() followed by terrain_feet(mask, swing = what it left), as one launch (wbc_gait_estimated_terrain_batch).  normals [12, N]
+        is IN/OUT: the contact law reads the previous tick's planes, then this tick's are written over them.  Returns dict(contact, phase, mask,
+        swing, events, f_est, normals, height, surf)."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        if normals is None:
+            raise ValueError("normals is a required in/out tensor ([12, N]; store unit normals before the first call)")
+        if f_est is None and want_f:
+            f_est = self.empty(3 * m.nf, N)
+        _, height, surf = self._terrain_out(N, normals, height, surf, want_surf)
+        _check(_terrain_lib().wbc_gait_estimated_terrain_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
+                                                               self._ptr(cmd, GAIT_CMD_WORDS, N),
+                                                               *self._contact_in_ptrs(N, Jc, r, f_prev, normals, contact), self._ptr(phase, 1, N),
+                                                               self._ptr(mask, 1, N, i32), self._ptr(swing, SWING_WORDS, N),
+                                                               self._ptr(events, 1, N, i32), self._ptr(f_est, 3 * m.nf, N),
+                                                               self._terrain_arg(terrain, N), self._ptr(height, m.nf, N), self._ptr(surf, m.nf, N),
+                                                               self._stream()), "wbc_gait_estimated_terrain_batch")
+        return dict(contact=contact, phase=phase, mask=mask, swing=swing, events=events, f_est=f_est, normals=normals, height=height, surf=surf)
 
     def compute_contact_estimate(self, Jc, r, f_prev, normals, contact=0):
         """Single-robot host-array form of contact_estimate (numpy float64, fp64 solvers; Jc [216] row-major 12 x 18): returns (contact, f_est[12],

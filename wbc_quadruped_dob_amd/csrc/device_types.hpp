@@ -276,6 +276,35 @@ template <class T> struct GaitEstimatedArgs {   // gait_estimated_kernel: g.cont
   GaitArgs<T> g;
   ContactIO<T> c;
 };
+// terrain heightfield (terrain.hip.hpp): the grid and what a call reads and writes -- BY VALUE like GroundIO.  The host (wbc_api.cpp, terrain_dev) has
+// checked the wbc_terrain and formed inv_cell, x_max, y_max in double, rounded to T; nothing is uploaded
+template <class T> struct DevTerrain {
+  const T* z;            // [n_tiles][ny][nx]
+  const int* tile;       // [N] (or [M]) or null = tile 0
+  int nx, ny;
+  unsigned tile_nodes;   // ny * nx; n_tiles * tile_nodes < 2^28, so every node lies within a 32-bit byte offset of z
+  T x0, y0, inv_cell, x_max, y_max;
+};
+template <class T> struct TerrainSampleArgs {   // terrain_sample_kernel
+  size_t M;
+  const T* xy;        // [2][M]
+  T* z; T* n; T* d;   // [M], [3][M], [M]; each or null
+  DevTerrain<T> g;
+};
+template <class T> struct TerrainOut {
+  T* normals; T* height;   // [12][N], [4][N]
+  T* surf;                 // [4][N] or null
+  DevTerrain<T> g;
+};
+template <class T> struct TerrainFeetArgs {   // terrain_feet_kernel
+  size_t N;
+  const T* q;
+  const int* mask; T* swing;   // both or neither
+  unsigned long long jpack;    // see SweepArgs::jpack
+  TerrainOut<T> t;
+};
+template <class T> struct GaitTerrainArgs { GaitArgs<T> g; TerrainOut<T> t; };                     // gait_terrain_kernel
+template <class T> struct GaitEstimatedTerrainArgs { GaitEstimatedArgs<T> e; TerrainOut<T> t; };   // gait_estimated_terrain_kernel: t.normals == e.c.normals
 
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc

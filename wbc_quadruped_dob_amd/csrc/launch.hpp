@@ -149,5 +149,12 @@ template <class T> hipError_t k_stick_integrate(const LaunchCtx& L, const DevMod
 // registers -- one launch
 template <class T> hipError_t k_contact_estimate(const LaunchCtx& L, const DevModel<T>* model, const ContactArgs<T>& a);
 template <class T> hipError_t k_gait_estimated(const LaunchCtx& L, const DevModel<T>* model, const GaitEstimatedArgs<T>& a);
+// terrain heightfield (terrain.hip.hpp): terrain_sample_kernel<T> is the sampling law at caller-given points; terrain_feet_kernel<T> the law under the
+// four feet of every state (normals, height, surf, and p1_z of the lifted feet's plans); gait_terrain_kernel<T> / gait_estimated_terrain_kernel<T> are
+// k_gait / k_gait_estimated followed by k_terrain_feet on the mask and swing they leave -- one launch each
+template <class T> hipError_t k_terrain_sample(const LaunchCtx& L, const TerrainSampleArgs<T>& a);
+template <class T> hipError_t k_terrain_feet(const LaunchCtx& L, const DevModel<T>* model, const TerrainFeetArgs<T>& a);
+template <class T> hipError_t k_gait_terrain(const LaunchCtx& L, const DevModel<T>* model, const GaitTerrainArgs<T>& a);
+template <class T> hipError_t k_gait_estimated_terrain(const LaunchCtx& L, const DevModel<T>* model, const GaitEstimatedTerrainArgs<T>& a);
 
 }  // namespace wbc

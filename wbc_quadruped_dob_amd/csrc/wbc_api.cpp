@@ -1720,6 +1720,99 @@ extern "C" int wbc_gait_estimated_batch(wbc_solver* s, size_t N, const void* q, 
   });
 }
 
+// ---- terrain heightfield: the struct's checks, the law at points, under the feet, and behind the two gait calls as one launch each
+static int terrain_check(const wbc_terrain* t) {
+  if (t->struct_size != sizeof(wbc_terrain)) return fail(WBC_E_INVALID, "wbc_terrain: wrong struct_size");
+  if (t->nx < 2 || t->ny < 2) return fail(WBC_E_INVALID, "wbc_terrain: nx and ny must be >= 2");
+  if (t->n_tiles < 1) return fail(WBC_E_INVALID, "wbc_terrain: n_tiles must be >= 1");
+  if (!std::isfinite(t->x0) || !std::isfinite(t->y0)) return fail(WBC_E_INVALID, "wbc_terrain: x0 and y0 must be finite");
+  if (!(t->cell > 0) || !std::isfinite(t->cell)) return fail(WBC_E_INVALID, "wbc_terrain: cell must be finite and > 0");
+  if (!t->z) return fail(WBC_E_INVALID, "wbc_terrain: z is null");
+  if ((unsigned long long)t->n_tiles * (unsigned long long)t->ny * (unsigned long long)t->nx >= (1ull << 28))
+    return fail(WBC_E_INVALID, "wbc_terrain: n_tiles * ny * nx must stay below 2^28 nodes");
+  return WBC_OK;
+}
+
+// (behind terrain_check)
+template <class T>
+static void terrain_dev(DevTerrain<T>& g, const wbc_terrain* t) {
+  g.z = (const T*)t->z; g.tile = t->tile; g.nx = t->nx; g.ny = t->ny; g.tile_nodes = (unsigned)t->ny * (unsigned)t->nx;
+  g.x0 = (T)t->x0; g.y0 = (T)t->y0; g.inv_cell = (T)(1.0 / t->cell);
+  g.x_max = (T)(t->x0 + (t->nx - 1) * t->cell); g.y_max = (T)(t->y0 + (t->ny - 1) * t->cell);
+}
+template <class T>
+static void terrain_out(TerrainOut<T>& o, const wbc_terrain* t, void* normals, void* height, void* surf) {
+  o.normals = (T*)normals; o.height = (T*)height; o.surf = (T*)surf;
+  terrain_dev(o.g, t);
+}
+
+extern "C" int wbc_terrain_sample_batch(wbc_solver* s, const wbc_terrain* terrain, size_t M, const void* xy, void* z, void* n, void* d, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (M == 0) return WBC_OK;
+  if (!terrain || !xy) return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = terrain_check(terrain)) return rc;
+  return launch_batch(s, M, stream, "terrain sample", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    TerrainSampleArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.M = M; a.xy = (const T*)xy; a.z = (T*)z; a.n = (T*)n; a.d = (T*)d;
+    terrain_dev(a.g, terrain);
+    return k_terrain_sample<T>(L, a);
+  });
+}
+
+extern "C" int wbc_terrain_feet_batch(wbc_solver* s, const wbc_terrain* terrain, size_t N, const void* q, const int* mask, void* swing, void* normals,
+                                      void* height, void* surf, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!terrain || !q || !normals || !height) return fail(WBC_E_INVALID, "null argument");
+  if ((mask == nullptr) != (swing == nullptr)) return fail(WBC_E_INVALID, "mask and swing are given both or neither");
+  if (const int rc = terrain_check(terrain)) return rc;
+  return launch_batch(s, N, stream, "terrain feet", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    TerrainFeetArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.q = (const T*)q; a.mask = mask; a.swing = (T*)swing; a.jpack = s->jpack;
+    terrain_out(a.t, terrain, normals, height, surf);
+    return k_terrain_feet<T>(L, dev_model<T>(s), a);
+  });
+}
+
+extern "C" int wbc_gait_terrain_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact, void* phase, int* mask,
+                                      void* swing, int* events, const wbc_terrain* terrain, void* normals, void* height, void* surf, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !phase || !mask || !swing || !terrain || !normals || !height) return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = terrain_check(terrain)) return rc;
+  return launch_batch(s, N, stream, "gait terrain", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GaitTerrainArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    gait_args(a.g, s, N, q, v, cmd, contact, phase, mask, swing, events);
+    terrain_out(a.t, terrain, normals, height, surf);
+    return k_gait_terrain<T>(L, dev_model<T>(s), a);
+  });
+}
+
+extern "C" int wbc_gait_estimated_terrain_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r,
+                                                const void* f_prev, void* normals, int* contact, void* phase, int* mask, void* swing, int* events,
+                                                void* f_est, const wbc_terrain* terrain, void* height, void* surf, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !Jc || !r || !f_prev || !normals || !contact || !phase || !mask || !swing || !terrain || !height)
+    return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = terrain_check(terrain)) return rc;
+  return launch_batch(s, N, stream, "gait estimated terrain", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GaitEstimatedTerrainArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    gait_args(a.e.g, s, N, q, v, cmd, nullptr, phase, mask, swing, events);
+    contact_io(a.e.c, s, Jc, r, f_prev, normals, contact, f_est, nullptr, nullptr);
+    terrain_out(a.t, terrain, normals, height, surf);
+    return k_gait_estimated_terrain<T>(L, dev_model<T>(s), a);
+  });
+}
+
 // ---- scored rollouts: the weights, the superset rollout, one tick's cost, the per-group selection
 extern "C" void wbc_score_params_default(wbc_score_params* p) {
   if (!p) return;
