@@ -1,6 +1,7 @@
 """CPU: host-side logic of the product library -- URDF reader parity with the independent Python parser,
 C-ABI symbol coverage against include/wbc_hip.h, and error behaviour.  No compute calls (no GPU here)."""
 import ctypes as C
+import glob
 import os
 import re
 import subprocess
@@ -146,9 +147,10 @@ def test_solver_options_struct_and_validation(hip_lib):
     assert "rollout_spw" in W.lib().wbc_last_error().decode()
     with pytest.raises(KeyError):
         W.SolverOptions.make({"no_such_switch": 1})
-    src = open(os.path.join(ROOT, "wbc_quadruped_dob_amd", "csrc", "wbc_api.cpp")).read() + \
-        open(os.path.join(ROOT, "wbc_quadruped_dob_amd", "csrc", "wbc_multi.cpp")).read()
-    assert "getenv" not in src
+    units = sorted(glob.glob(os.path.join(ROOT, "wbc_quadruped_dob_amd", "csrc", "*.cpp")))
+    assert len(units) >= 2
+    for unit in units:
+        assert "getenv" not in open(unit).read(), unit
 
 
 def test_shard_range_c_abi_matches_python_sharding(hip_lib):
@@ -289,6 +291,14 @@ def test_dispatch_thresholds_cover_the_documented_switches(hip_lib):
     assert [W.plan_tick(n, "f64", ob)["fused"] for n, ob in ((8192, 0), (8193, 0), (11264, 0), (8192, 1), (12288, 1), (12289, 1))] == [3, 2, 2, 1, 2, 2]
     assert [W.plan_tick(n, "f64", 0, options={"fused_max": 11264})["fused"] for n in (8193, 11264, 11265)] == [1, 1, 2]   # (a caller who names the one-launch tick's limit keeps it)
 
+
+def test_plan_sweep_reported_thresholds_are_every_switch():
+    """tools/plan_sweep.bin is the planner's two HIP-free units and nothing else (tools/Makefile: the host compiler, no HIP library).  --check walks
+    wbc_plan_tick over every N = 1 .. 2^21 in 64 configurations and fails unless wbc_dispatch_thresholds reports exactly the batch sizes at which
+    the plan switches: a threshold added to plan_tick and forgotten in the candidate list of wbc_dispatch_thresholds fails here."""
+    r = subprocess.run([os.path.join(ROOT, "tools", "plan_sweep.bin"), "--check"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    assert len(r.stdout.splitlines()) == 64 + 1
 
 
 

@@ -28,7 +28,7 @@ BUDGET = [
     (r"observer_kernelI[df]", 256),
     (r"qp_lane_kernelI[df]", 256),
     (r"qp_tile_kernelI[df]Lb[01]ELi\d+E", 256), (r"qp_group16_kernelI[df]", 256), (r"qp_list_kernelI[df]", 256),
-    # the host sizes fp64 tiles for THREE resident workgroups per CU (wbc_api.cpp: one round of 768): that needs <= 168 registers
+    # the host sizes fp64 tiles for THREE resident workgroups per CU (tick_plan.cpp: one round of 768): that needs <= 168 registers
     (r"qp_tile_kernelIdLb[01]ELi(32|36|40|44|48|52|56|60|64)ELb0E", 168),
     # ... and since the QP weights stay scalar in the tiled body, the fp32 tiles and the hand-over list kernel hold three wavefronts per SIMD too
     (r"qp_tile_kernelIfLb[01]ELi(32|36|40|44|48|52|56|60|64|72|80|88|96|104|112|120|128)ELb0E", 168), (r"qp_list_kernelI[df]Lb[01]ELb0E", 168),

@@ -276,7 +276,7 @@ template <class T> struct GaitEstimatedArgs {   // gait_estimated_kernel: g.cont
   GaitArgs<T> g;
   ContactIO<T> c;
 };
-// terrain heightfield (terrain.hip.hpp): the grid and what a call reads and writes -- BY VALUE like GroundIO.  The host (wbc_api.cpp, terrain_dev) has
+// terrain heightfield (terrain.hip.hpp): the grid and what a call reads and writes -- BY VALUE like GroundIO.  The host (api_walk.cpp, terrain_dev) has
 // checked the wbc_terrain and formed inv_cell, x_max, y_max in double, rounded to T; nothing is uploaded
 template <class T> struct DevTerrain {
   const T* z;            // [n_tiles][ny][nx]

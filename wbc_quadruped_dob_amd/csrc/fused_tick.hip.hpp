@@ -2,7 +2,7 @@
 // consecutive states; its wavefronts are ROLES that hand the 66-word step workspace over in LDS (no launch boundary, no round trip of the workspace through
 // memory), and the M / h / Jc stores -- which no role reads back -- drain behind the QP.  At these sizes (the bench default: 4 096 fp64 states = 256 CUs x 16)
 // every stage is latency-bound: the kernel lasts as long as the dependent chain of its workgroup's hardest QP.
-// Which batches take it: the planner (wbc_api.cpp; the table of DESIGN.md 5); above it the pair tick below and the tile
+// Which batches take it: the planner (tick_plan.cpp; the table of DESIGN.md 5); above it the pair tick below and the tile
 // tick (tile_tick.hip.hpp) take over, and large batches keep the two-launch tick, whose sweep is bandwidth-bound and wants every lane of eight wavefronts per CU.
 // History of the layout and of what was measured on the way: docs/DESIGN_R04.md, docs/DESIGN_R05.md, docs/DESIGN_HISTORY.md.
 #pragma once

@@ -62,7 +62,7 @@ hipError_t k_qp<Scalar>(const LaunchCtx& L, bool rhat, int tile, const DevParams
     else WBC_KLAUNCH(L, (qp_list_kernel<T, false>), grid, dim3(64), prm, a, jmap, list);
     return hipGetLastError();
   }
-  // tile sizes in small steps so that the host can launch ONE round of resident workgroups (wbc_api.cpp): fp64 tiles keep three workgroups on a
+  // tile sizes in small steps so that the host can launch ONE round of resident workgroups (tick_plan.cpp, plan_tick): fp64 tiles keep three workgroups on a
   // CU (768 at once) up to 64 states per tile, fp32 tiles two (512) -- hence steps of 4 from 32 to 64 for fp64, of 8 from 64 to 128 for fp32
   if (body == 2) {
     if constexpr (std::is_same<T, float>::value) {

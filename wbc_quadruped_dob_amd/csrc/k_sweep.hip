@@ -33,7 +33,7 @@ static hipError_t sweep_mode(const LaunchCtx& L, const DevModel<Scalar>* model, 
 
 template <>
 hipError_t k_dyn_sweep<Scalar>(const LaunchCtx& L, int mode, const DevModel<Scalar>* model, const DevParams<Scalar>& prm, const SweepArgs<Scalar>& a) {
-  switch (mode) {   // (the combinations the host side launches: wbc_api.cpp)
+  switch (mode) {   // (the combinations the host side launches: api_tick.cpp, step_impl)
     case 0: return sweep_mode<0>(L, model, prm, a);                                   // pf only
     case SW_MATS: return sweep_mode<SW_MATS>(L, model, prm, a);
     case SW_OBS: return sweep_mode<SW_OBS>(L, model, prm, a);

@@ -11,7 +11,7 @@
 // 256-thread workgroup the constant table sat behind a 68 kB array in LDS, out of reach of the 16-bit ds_read offset.  With
 // the carried values pinned per joint, one LDS object (table first) and the forward sweep's per-joint state parked in LDS:
 // 170 VGPRs, no scratch, 112 us fp64 / 57 us fp32 -- default for fp64 observer-on batches from 65 536 states on
-// (fp32: 98 304); see wbc_api.cpp for the A/B.
+// (fp32: 98 304); see plan_consts.hpp for the A/B.
 // Same lane mapping as the sweep (lane = 16*leg + state), same formulas as the observer role of the fused tick
 // (rnea_step_body<RS_OBS | RS_OBSW>): beta = C^T v - g from the momentum recursion, see docs/DESIGN_R04.md section 3.
 #pragma once

@@ -140,7 +140,7 @@
 // 0: every tick stores its M / Jc / pf (A/B)
     at.skip_mats = (1 && t < horizon - 1) ? 1 : 0;   // M, Jc, pf of the LAST tick are what the caller finds in its buffers (as with per-tick launches)
     if (t > 0) at.skip_consts = 1;   // the structural zeros / ones of M, Jc were written by tick 0 of THIS launch into the same buffers (the mass_jac role's
-                                     // ~55 store instructions per tick sit in front of the integrator's factorisation: wbc_api.cpp, rollout_persistent)
+                                     // ~55 store instructions per tick sit in front of the integrator's factorisation: api_rollout.cpp, rollout_persistent)
 #ifdef WBC_FUSED_STAMP   // diagnostic build: the last tick's role timestamps go out through the pf output
     double* const rstamp = (t == horizon - 1) ? (double*)a.pf : nullptr;
     const unsigned rstampN = (unsigned)n_tick;
