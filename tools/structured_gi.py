@@ -137,6 +137,7 @@ class StructuredGI:
         eps = np.finfo(float).eps
         Rnorm, it, status = 1.0, 0, 0
         self.trace = []     # one letter per trip: A full step (the candidate is added), P partial step + drop, D dual-only step + drop
+        self.drops = []     # per drop: (index of its trip in the trace, rows left on the foot the constraint leaves)
         slack = lambda c, xx: self.C[c].dot(xx[3 * (c // 6):3 * (c // 6) + 3]) - self.rhs[c]
 
         def refresh(k):
@@ -146,6 +147,7 @@ class StructuredGI:
             k = l // 6
             Pold = P[k]
             act[k].remove(l); order.remove(l); del u[l]
+            self.drops.append((len(self.trace), len(act[k])))   # (this trip's index, rows left on the foot)
             refresh(k)
             if self.sm:   # rank-one UPDATE of G (P grows by w w^T): G^-1 -= (G^-1 bb)(G^-1 bb)^T / (1 + bb . G^-1 bb)
                 D = P[k] - Pold

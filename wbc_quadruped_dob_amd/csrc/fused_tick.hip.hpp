@@ -59,9 +59,10 @@ template <class T, bool OBSERVER, bool MATS, bool WARM = false> constexpr bool f
 // fmas in the fp32 tick), so M came out with other last bits than the warm tick, the two-launch tick and every earlier build give -- and those are compared bit for bit
 // (tests/test_gpu_warm.py).  fp64 has no packed arithmetic: its instruction mix, and its bits, are those of the plain-store build.
 template <class T, bool MATS, bool WARM> constexpr int fused_store() { return (MATS && !WARM && sizeof(T) == 8) ? ST_WT : ST_PLAIN; }
-// The QP wavefronts' own stores -- tau, f, status, iters, the active set: the tick's LAST stores -- keep plain stores: write-through there gave +1.5 % at 4 096 fp64
-// states, 2.4 times the parent's run-to-run spread and so short of the gain rule on its own, and cost the observer-on tick 1 % (docs/DESIGN_HISTORY.md).
-// The QP trips of the cold fp64 observer-off tick branch around the search and the add-commit that no live row of the wavefront needs (qp_struct16.hip.hpp, SKIP).
+// The QP wavefronts' own stores -- tau, f, status, iters, the active set: the tick's LAST stores -- are plain stores in the observer-on and warm ticks: write-through
+// there gave +1.5 % at 4 096 fp64 states, short of the gain rule on its own, and cost the observer-on tick 1 % (docs/DESIGN_HISTORY.md).
+// The cold fp64 observer-off tick is the one whose QP ends the kernel.  Its trips branch around the add-commit that no live row of the wavefront needs (qp_struct16.hip.hpp,
+// SKIP), and with the same flag its QP runs the same arithmetic in fewer instructions and stores its results write-through (DIET there; tools/chain_count.py counts the chain).
 template <class T, bool OBSERVER, bool WARM> constexpr bool fused_trip_skip() { return !OBSERVER && !WARM && sizeof(T) == 8; }
 template <class T, bool OBSERVER, bool MATS, bool WARM = false> constexpr int fused_threads() { return OBSERVER ? 384 + 64 * FUSED_OBS_WAVES : (fused_split_h<T, OBSERVER, MATS, WARM>() ? 448 : 384); }
 // WARM: the QP of every state starts from the active set in qa.aset_in (wbc_step_batch_warm: dependent ticks of a closed loop)

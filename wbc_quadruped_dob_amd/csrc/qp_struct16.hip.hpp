@@ -101,6 +101,15 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   constexpr bool SPEC = WSLDS && RHAT && WARM == 0 && !PRE && !TILED;
   static_assert(!(WARM != 0 && PRE), "warm starts set their blocks up themselves");
   static_assert(!SKIP || (WARM == 0 && !SPEC && !PRE && STG == 0), "SKIP leaves a finished row's factors stale: only where nothing reads them behind the loop");
+  // DIET (with SKIP: the cold fp64 observer-off one-launch tick, whose kernel lasts as long as the instruction stream of its hardest wavefront's QP --
+  // tools/chain_count.py): the same arithmetic with fewer instructions around it.  (a) the tail's address arithmetic is formed in the idle stretch in front of
+  // the lever-arm wait and held, (g) and the tables that need no lever arm are written there; (b) the tables the trip indexes at run time are addressed from
+  // LDS byte addresses the compiler cannot fold into the instruction's offset field -- folded, the bases lie beyond the reach of ds_read2_b64 and every trip
+  // re-adds them; (c) in the drop path the scratch vector is read by every row and selected, the set's flags are cleared by selects; (d) f, tau, status, iters
+  // and the set -- the tick's last stores -- go out write-through; (e) the loop is tested at its bottom, (f) on ip alone.  Every other instantiation keeps its
+  // code (docs/DESIGN_HISTORY.md: the counts per piece, the measurements).
+  constexpr bool DIET = SKIP;
+  typedef __attribute__((address_space(3))) T LdsT;
   WBC_QP_ROW_PROLOGUE
   S16Lds<T>* Lp;
   if constexpr (STG != 0) Lp = (S16Lds<T>*)who.tab;     // (staged tiles: this wavefront's tables live in the kernel's dynamic LDS, beside the image)
@@ -151,6 +160,21 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   T cAx, cAy, cAz, rA, cBx = 0, cBy = 0, cBz = 0;
   const bool hasB = c3 < 2;
   if constexpr (CONS_EARLY) WBC_QP_FORM_ROWS;
+  // (DIET a) byte offsets of my f and tau words, of my tau_partial and own-leg Jacobian words in the workspace image, my joint's index
+  unsigned f_off = 0, tau_off = 0, wv_off = 0, wj_off = 0;
+  if constexpr (DIET) {
+    const int jm0 = (int)((unsigned)(a.jpack >> (4 * (v & 15))) & 15u);
+    f_off = (unsigned)QP_ROW_BYTES_(v, s32); tau_off = (unsigned)QP_ROW_BYTES_(jm0, s32);
+    wv_off = (unsigned)(((WS_TAUP + v) * 16 + (int)(tx >> 4)) * (int)sizeof(TS)); wj_off = (unsigned)(((WS_JCL + 9 * f + c3) * 16 + (int)(tx >> 4)) * (int)sizeof(TS));
+    asm volatile("" : "+v"(f_off), "+v"(tau_off), "+v"(wv_off), "+v"(wj_off));
+    // ... and the tables that need no lever arm are written here: my two constraint normals, my row of P_k = I (LDS is in order within a wavefront, and the
+    // fence behind the lever-arm table below covers them)
+    static_assert(CONS_EARLY, "DIET: the constraint rows are formed in front of the lever-arm wait");
+    T* c = Cl + 3 * (2 * l16);
+    c[0] = cAx; c[1] = cAy; c[2] = cAz; c[3] = cBx; c[4] = cBy; c[5] = cBz;
+    T* pr = Pl + 16 * f + 4 * c3;
+    pr[0] = c3 == 0 ? (T)1 : (T)0; pr[1] = c3 == 1 ? (T)1 : (T)0; pr[2] = c3 == 2 ? (T)1 : (T)0;
+  }
   if constexpr (WSLDS) { if (sync) qp_wait(sync->geom, sync->need_geom); }
   WBC_QSTAMP(2);
   T d_me = 0;
@@ -199,10 +223,12 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   int id_s = -1, qk = 0;
   T* const prow = Pl + 16 * f + 4 * c3;   // my row of foot f's P in the LDS table (the spare lane owns a dummy row: no predicate on the write)
   {
-    T* c = Cl + 3 * (2 * l16);
-    c[0] = cAx; c[1] = cAy; c[2] = cAz; c[3] = cBx; c[4] = cBy; c[5] = cBz;
-    // tables addressed by the run-time foot index kp: P_k = I, lever arm d_k (zero for a swing foot)
-    { T* pr = Pl + 16 * f + 4 * c3; pr[0] = Pr0; pr[1] = Pr1; pr[2] = Pr2; }
+    if constexpr (!DIET) {   // (DIET: written in front of the lever-arm wait)
+      T* c = Cl + 3 * (2 * l16);
+      c[0] = cAx; c[1] = cAy; c[2] = cAz; c[3] = cBx; c[4] = cBy; c[5] = cBz;
+      // tables addressed by the run-time foot index kp: P_k = I, lever arm d_k (zero for a swing foot)
+      { T* pr = Pl + 16 * f + 4 * c3; pr[0] = Pr0; pr[1] = Pr1; pr[2] = Pr2; }
+    }
     if (isvar) Dl[3 * f + c3] = c3 == 0 ? dqx : (c3 == 1 ? dqy : dqz);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_wave_barrier();
@@ -423,6 +449,12 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
   // ~70 instructions whose results nothing reads: a trip is bound by the issue rate of a lone wavefront, not by latency.  The forms that read
   // the factors or the multipliers behind the loop (WARM, SPEC, PRE, STG) keep SKIP off.  The same branch around the search of a trip on which
   // no row takes its full step was measured and not kept: it puts the ratio test in front of the search on every trip (docs/DESIGN_HISTORY.md).
+  // (DIET b) LDS byte addresses of the three run-time indexed tables, opaque to the compiler
+  unsigned cl_a = 0, pl_a = 0, dl_a = 0;
+  if constexpr (DIET) {
+    cl_a = (unsigned)(size_t)(LdsT*)Cl; pl_a = (unsigned)(size_t)(LdsT*)Pl; dl_a = (unsigned)(size_t)(LdsT*)Dl;
+    asm volatile("" : "+v"(cl_a), "+v"(pl_a), "+v"(dl_a));
+  }
   int ip = -1, status = 0, iter = 0;
   int iter0 = 0;   // (SPEC) trips of the phase on b~: the second phase has the whole of max_iter (it used to get what phase 0 left)
   bool done = !live;
@@ -477,8 +509,16 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
     sip = val;
     done = done || !found;
   }
-  while (__ballot(!done && ip >= 0) != 0ull) {   // (every trip counts against max_iter in every row that is still working)
-    bool go = !done && ip >= 0;
+  // (every trip counts against max_iter in every row that is still working)
+  // (DIET e) the loop is tested at its BOTTOM, behind one test in front of it.  The compiler does not rotate a loop whose header holds a ballot, and the
+  // top-tested form pays an exit stub and, in the latch, three scalar instructions per carried flag (done, the set's two flags) on every trip
+  // (DIET f) "finished" is kept in ip alone: a row has a candidate exactly while it works (true on entry: the first search sets ip = -1 with done; every
+  // trip ends with ip = -1 in the rows it finished), so the loop's test and `go` are one compare, and `done` is a flag of the trip, not of the loop
+  if (!DIET || __ballot(ip >= 0) != 0ull)
+  for (;;) {
+    if constexpr (!DIET) { if (__ballot(!done && ip >= 0) == 0ull) break; }
+    if constexpr (DIET) done = false;
+    bool go = DIET ? ip >= 0 : (!done && ip >= 0);
     iter += go ? 1 : 0;
     const bool over = go && iter - iter0 > prm.max_iter;
     status = over ? 1 : status;
@@ -487,10 +527,20 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
     const int ipc = ip < 0 ? 0 : ip;
     const int lp = (ipc >> 1) & 15, kp = lp >> 2;
     // ---- candidate normal, P and lever arm of its foot (LDS, run-time indices); v, b formed by every lane
-    const T np0 = Cl[3 * ipc], np1 = Cl[3 * ipc + 1], np2 = Cl[3 * ipc + 2];
-    const T* pk_ = Pl + 16 * kp;
-    const T pxx = pk_[0], pxy = pk_[1], pxz = pk_[2], pyy = pk_[5], pyz = pk_[6], pzz = pk_[10];
-    const T dkx = Dl[3 * kp], dky = Dl[3 * kp + 1], dkz = Dl[3 * kp + 2];
+    T np0, np1, np2, pxx, pxy, pxz, pyy, pyz, pzz, dkx, dky, dkz;
+    if constexpr (DIET) {
+      const LdsT* const cq = (const LdsT*)(size_t)(cl_a + 24u * (unsigned)ipc);
+      const LdsT* const pq = (const LdsT*)(size_t)(pl_a + 128u * (unsigned)kp);
+      const LdsT* const dq = (const LdsT*)(size_t)(dl_a + 24u * (unsigned)kp);
+      np0 = cq[0]; np1 = cq[1]; np2 = cq[2];
+      pxx = pq[0]; pxy = pq[1]; pxz = pq[2]; pyy = pq[5]; pyz = pq[6]; pzz = pq[10];
+      dkx = dq[0]; dky = dq[1]; dkz = dq[2];
+    } else {
+      np0 = Cl[3 * ipc]; np1 = Cl[3 * ipc + 1]; np2 = Cl[3 * ipc + 2];
+      const T* pk_ = Pl + 16 * kp;
+      pxx = pk_[0]; pxy = pk_[1]; pxz = pk_[2]; pyy = pk_[5]; pyz = pk_[6]; pzz = pk_[10];
+      dkx = Dl[3 * kp]; dky = Dl[3 * kp + 1]; dkz = Dl[3 * kp + 2];
+    }
     const T v0 = pxx * np0 + pxy * np1 + pxz * np2, v1 = pxy * np0 + pyy * np1 + pyz * np2, v2 = pxz * np0 + pyz * np1 + pzz * np2;
     const T vv = v0 * v0 + v1 * v1 + v2 * v2;
     T bb[6];
@@ -589,7 +639,11 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
       const int kq = dropg ? kmin : 0;                 // lane (within the row) of the blocking slot
       const int kd = kq >> 2, sd = kq & 3;             // its foot and slot
       const int cid = gread(id_s, kq, rowbase);        // the constraint that leaves
-      if (dropg && l16 == ((cid >> 1) & 15)) { if (cid & 1) actB = false; else actA = false; }
+      if constexpr (DIET) {
+        const bool gone = dropg && l16 == ((cid >> 1) & 15);
+        actA = actA && !(gone && !(cid & 1));
+        actB = actB && !(gone && (cid & 1));
+      } else if (dropg && l16 == ((cid >> 1) & 15)) { if (cid & 1) actB = false; else actA = false; }
       const bool inq = dropg && f == kd;
       const T Po0 = Pr0, Po1 = Pr1, Po2 = Pr2;
       {  // close the hole in the slot list of foot kd
@@ -622,7 +676,11 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
         // (rows that do not drop read whatever the scratch holds: zeroed, so that their G_A^-1 sees an update by exactly nothing)
-        const T h0 = dropg ? Wl[0] : (T)0, h1 = dropg ? Wl[1] : (T)0, h2 = dropg ? Wl[2] : (T)0;
+        T h0, h1, h2;
+        if constexpr (DIET) {   // (every row reads the scratch -- whatever it holds -- and selects: three loads side by side, no masked regions around them)
+          const T r0 = Wl[0], r1 = Wl[1], r2 = Wl[2];
+          h0 = dropg ? r0 : (T)0; h1 = dropg ? r1 : (T)0; h2 = dropg ? r2 : (T)0;
+        } else { h0 = dropg ? Wl[0] : (T)0; h1 = dropg ? Wl[1] : (T)0; h2 = dropg ? Wl[2] : (T)0; }
         const int kdc = dropg ? kd : 0;
         const T ex = Dl[3 * kdc], ey = Dl[3 * kdc + 1], ez = Dl[3 * kdc + 2];
         T bh[6];
@@ -642,6 +700,10 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
       }
     }
     SEG(5);
+    if constexpr (DIET) {
+      ip = done ? -1 : ip;
+      if (__ballot(ip >= 0) == 0ull) break;
+    }
   }
   if constexpr (SPEC) {
     if (ph == 0) {
@@ -713,6 +775,7 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
     const int aset_fin = (int)(((unsigned)(ba >> rowbase) & 0xFFFFu) | (((unsigned)(bbm >> rowbase) & 0xFFFFu) << 16));
     if constexpr (WARM == 2) { if (l16 == 0) *carry = aset_fin; }   // (LDS: read back by this row in the next tick -- program order of one wavefront)
     if constexpr (STG != 0) { if (live && l16 == 0) who.iimg[3 * who.tile + stg_slot] = aset_fin; }
+    else if constexpr (DIET) { if (a.aset_out && live && l16 == 0) __hip_atomic_store(a.aset_out + s32, aset_fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     else if (a.aset_out && live && l16 == 0) a.aset_out[s32] = aset_fin;
   }
   bool to_mem = true;   // (QpSync::skip_out: wavefront-uniform)
@@ -724,6 +787,47 @@ WBC_DEV void qp_struct16_body(const DevParams<TS>& prm, const QpArgs<TS>& a, con
       if (sync->hand) { qp_wait(sync->hand_flag, sync->need_hand); from_hand = true; hand_img = (const TS*)sync->hand; }
     }
   }
+  if constexpr (DIET) {
+    // the same map and the same words as below, from the offsets formed in front of the lever-arm wait; the stores write-through (device_types.hpp, store_out:
+    // nothing in the launch reads them back, and they are the kernel's last -- plain, they wait in L2 for the write-back at the kernel's end)
+    static_assert(WSLDS && !RHAT && STG == 0 && sizeof(TS) == 8, "DIET: the cold fp64 observer-off one-launch tick");
+    if (live) {
+      T taup = 0, jl0 = 0, jl1 = 0, jl2 = 0;
+      if (isvar) {
+        const char* const wb = (const char*)wsl;
+        taup = (T)*(const TS*)(wb + wv_off);
+        if (from_hand) {
+          const int hslot = 16 * f + (int)((tx >> 4) & 15);
+          jl0 = (T)hand_img[(24 + c3) * 64 + hslot]; jl1 = (T)hand_img[(27 + c3) * 64 + hslot]; jl2 = (T)hand_img[(30 + c3) * 64 + hslot];
+        } else {
+          jl0 = (T)*(const TS*)(wb + wj_off); jl1 = (T)*(const TS*)(wb + wj_off + 3 * 16 * sizeof(TS)); jl2 = (T)*(const TS*)(wb + wj_off + 6 * 16 * sizeof(TS));
+        }
+      }
+      const T xq0 = dppx<0x00>(x_me), xq1 = dppx<0x55>(x_me), xq2 = dppx<0xAA>(x_me);
+      if (isvar) {
+        const T fx = on ? xq0 : (T)0, fy = on ? xq1 : (T)0, fz = on ? xq2 : (T)0;
+        if (to_mem) {
+          store_out<ST_WT>((TS*)((char*)a.f + f_off), (TS)(on ? x_me : (T)0));
+          store_out<ST_WT>((TS*)((char*)a.tau + tau_off), (TS)(taup - (jl0 * fx + jl1 * fy + jl2 * fz)));
+        }
+        if (sync && sync->res) {
+          const int jm = (int)((unsigned)(a.jpack >> (4 * (v & 15))) & 15u);
+          TS* rs = (TS*)sync->res + (int)(tx >> 4);
+          rs[(RES_F + v) * 16] = (TS)(on ? x_me : (T)0);
+          rs[(RES_TAU + jm) * 16] = (TS)(taup - (jl0 * fx + jl1 * fy + jl2 * fz));
+        }
+      }
+      if (sync && sync->stat && l16 == 0) sync->stat[(int)(tx >> 4)] = status;
+      if (l16 == 0 && to_mem) {
+        __hip_atomic_store(a.status + s32, status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef WBC_QP_STAMP
+        GST_ITERS(iter);
+#else
+        if (a.iters) __hip_atomic_store(a.iters + s32, iter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+      }
+    }
+  } else
   if (live) {
     T taup = 0, jl0 = 0, jl1 = 0, jl2 = 0;
     int jm = 0;
