@@ -256,6 +256,30 @@ class QuadrupedWBC {
           "wbc_gait_estimated_terrain_batch");
   }
 
+  // Foothold selection (wbc_hip.h, "Foothold selection"): a cost per node of the map (terrainCost, once per map and parameter set) and, per lifted foot,
+  // the cheapest node near the gait rule's foothold, latched until the foot is down.  cost [n_tiles][ny][nx], hold [8][N] and latch [N] (0 before the
+  // first tick) are caller-owned DEVICE buffers.  gaitTerrainSelect / gaitEstimatedTerrainSelect are gaitTerrain / gaitEstimatedTerrain with the
+  // selection between the gait rule and the terrain rule, one launch each.  (The argument order of the C calls.)
+  void setFootholdParams(const wbc_foothold_params& p) { check(wbc_solver_set_foothold_params(solver_, &p), "wbc_solver_set_foothold_params"); }
+  void terrainCost(const wbc_terrain& t, void* cost, void* stream = nullptr) { check(wbc_terrain_cost_batch(solver_, &t, cost, stream), "wbc_terrain_cost_batch"); }
+  void footholdSelect(const wbc_terrain& t, const void* cost, size_t N, const int* mask, void* swing, void* hold, int* latch, void* stream = nullptr) {
+    check(wbc_foothold_select_batch(solver_, &t, cost, N, mask, swing, hold, latch, stream), "wbc_foothold_select_batch");
+  }
+  void gaitTerrainSelect(size_t N, const void* q, const void* v, const void* cmd, const int* contact /* may be nullptr */, void* phase, int* mask,
+                         void* swing, int* events /* may be nullptr */, const wbc_terrain& t, void* normals, void* height, void* surf /* may be nullptr */,
+                         const void* cost, void* hold, int* latch, void* stream = nullptr) {
+    check(wbc_gait_terrain_select_batch(solver_, N, q, v, cmd, contact, phase, mask, swing, events, &t, normals, height, surf, cost, hold, latch, stream),
+          "wbc_gait_terrain_select_batch");
+  }
+  void gaitEstimatedTerrainSelect(size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r, const void* f_prev,
+                                  void* normals /* in/out */, int* contact, void* phase, int* mask, void* swing, int* events /* may be nullptr */,
+                                  void* f_est /* may be nullptr */, const wbc_terrain& t, void* height, void* surf /* may be nullptr */, const void* cost,
+                                  void* hold, int* latch, void* stream = nullptr) {
+    check(wbc_gait_estimated_terrain_select_batch(solver_, N, q, v, cmd, Jc, r, f_prev, normals, contact, phase, mask, swing, events, f_est, &t, height,
+                                                  surf, cost, hold, latch, stream),
+          "wbc_gait_estimated_terrain_select_batch");
+  }
+
   // Joint torque limits (wbc_hip.h, "Joint torque limits behind a tick").  effortLimits(): the URDF's <limit effort> per joint in jointNames() order,
   // HUGE_VAL where it gives none.  setTorqueLimits(): the limits the post-pass enforces (one value > 0 per joint; empty = back to the URDF's).
   std::vector<double> effortLimits() const {

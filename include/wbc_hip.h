@@ -782,6 +782,91 @@ int wbc_gait_estimated_terrain_batch(wbc_solver* s, size_t N, const void* q, con
                                      void* f_est /* may be NULL */, const wbc_terrain* terrain, void* height /* out [4][N] */,
                                      void* surf /* may be NULL */, void* stream);
 
+/* Foothold selection: a terrain cost map and a per-foot search on the device.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct, call,
+ * default or kernel output changes; detect it by these symbols).  The terrain calls above give a lifted foot the height of its foothold; the foothold
+ * itself lands wherever the gait rule puts it, on an edge as readily as on a flat spot.  These calls move it to a nearby node of the map that is cheap.
+ * Cost map, wbc_terrain_cost_batch: one launch per map at set-up time.  cost is caller-owned DEVICE memory [n_tiles][ny][nx] of the solver's scalar
+ * type, laid out like terrain->z.  Per node c = (ix, iy) of a tile, in T, no product contracted:
+ *   step   = max over |dx|, |dy| <= margin of |z(clip(ix+dx), clip(iy+dy)) - z(c)|        (indices clipped to the grid; subtraction, abs and max
+ *                                                                                           only: exact)
+ *   sx     = (z(ix+1, iy) - z(ix-1, iy)) inv_cell / 2;  at ix = 0 and ix = nx-1 the difference is one-sided and multiplied by inv_cell alone
+ *   sy     likewise;   slope2 = sx^2 + sy^2
+ *   cost   = w_step step + w_slope slope2
+ * Selection law, per state and foot k, behind the gait rule of the same tick.  Caller-owned state, advanced in place:
+ *   hold  [8][N]   rows 2k, 2k+1 = the latched x, y of foot k.  Needs no initial value.
+ *   latch [N] int  in: bit k = foot k has a latched foothold (only bits 0-3 are read; the caller stores 0 before the first tick).
+ *                  out: bits 0-3 = the new latches, bit 4+k = foot k was selected THIS tick.
+ * With `bit` the foot's bit of mask and sw its nine plan words (x = sw[3], y = sw[4] as the gait rule left them):
+ *   bit set (stance)         latch bit k := 0; nothing else is touched
+ *   lifted and latched       sw[3], sw[4] := hold; no search.  A POINT is latched, not an offset: with retarget = 1 the nominal foothold drifts by more
+ *                            than half a cell during a swing, and a latched offset put 25 % / 59 % of the touchdowns of the loops below on costly nodes
+ *   lifted, not latched      jx = clamp((int)floor((x - x0) inv_cell + 0.5), 0, nx-1), jy likewise: the nearest node;  c0 = cost[jx, jy]
+ *                            c0 <= cost_ok, or sw[8] > u_max sw[7] (too late in the swing to move the target), or radius = 0: the foot is KEPT -- no
+ *                            word is written, it is not latched, and it is examined again next tick
+ *                            otherwise scan iy = jy-R .. jy+R (outer, ascending), ix = jx-R .. jx+R (inner, ascending), each range clipped to the grid:
+ *                              xc = x0 + ix cell,  yc = y0 + iy cell,  J = cost[ix, iy] + w_dist ((xc - x)^2 + (yc - y)^2)
+ *                            and take the first candidate with strictly smaller J (if no node of the window is below cost_ok the minimum is still
+ *                            taken).  hold := (xc, yc); sw[3], sw[4] := hold; latch bit k := 1; bit 4+k := 1
+ * p1_z (word 5) is written afterwards by the terrain rule of wbc_terrain_feet_batch at the plan's own (p1_x, p1_y); a selected foothold is a node, so on
+ * a dyadic grid p1_z is that node's own bits.  x0, y0 and cell arrive rounded to T; on a dyadic grid xc, yc are exact.
+ *   wbc_foothold_select_batch               the law alone, on mask and swing as a gait call left them
+ *   wbc_gait_terrain_select_batch           wbc_gait_terrain_batch's arguments + cost, hold, latch: ONE launch whose outputs are those of wbc_gait_batch,
+ *                                           then wbc_foothold_select_batch, then wbc_terrain_feet_batch(mask, swing) -- bit for bit, but for normals,
+ *                                           height and surf, which are wbc_gait_terrain_batch's own bits (they agree with wbc_terrain_feet_batch's
+ *                                           to rounding, as that call's do).  With radius = 0 and no latch bit set its other outputs are
+ *                                           wbc_gait_terrain_batch's bit for bit.
+ *   wbc_gait_estimated_terrain_select_batch the same behind wbc_gait_estimated_batch
+ * The walking tick stays at four launches with no host work between them:
+ *   gait[_estimated]_terrain_select -> reference_swing -> step -> integrate_ground[_stick]
+ * Per tick the common path costs one gather of cost per lifted foot; the window (at most 81 gathers) runs only in the lanes that start a selection.
+ * The defaults
+ *   radius = 3, margin = 1, w_step = 1, w_slope = 2^-7, w_dist = 4 (1/m), cost_ok = 8.75e-3, u_max = 0.75
+ * were fixed on the CPU with the numpy restatement of this law (tests/foothold_ref.py) in the walking loop of tests/terrain_ref.py (4 robots, 512 ticks
+ * of 2^-10 s, the stiction plant, 4 tiles of 64 x 48 nodes, cell 2^-6).  radius, margin, w_step, w_dist and u_max are the prototype's.  The rule for the
+ * other two: on that file's "flat" ground and "tiles" (the rippled ramps) no node a foot is ever aimed at may exceed cost_ok, so that those loops
+ * reproduce the loops without selection bit for bit; cost_ok is the largest cost aimed at there times 1.5, and it must lie below half the cost of a
+ * ridge-adjacent node of the test terrain (flat ground + 2 cm ridges along y every 8 or every 4 cells: 0.02, so below 0.01).  Tried, w_slope -> the
+ * largest cost aimed at on the tiles -> times 1.5:  0 -> 5.024e-3 -> 7.54e-3;  2^-7 -> 5.832e-3 -> 8.75e-3;  2^-6 -> 6.639e-3 -> 9.96e-3 (0.4 % below the
+ * bound);  2^-5 -> 8.255e-3 -> 1.24e-2 (fails).  2^-7 is the largest that keeps a margin (12.5 %).  On flat ground every cost is 0.
+ * With these, in the loops on the ridges (32 touchdowns each, every QP status 0): touchdowns on a node whose 3 x 3 neighbourhood holds a height step
+ * fall from 41 % to 0 (ridges every 8 cells) and from 84 % to 0 (every 4 cells; without selection one robot there walks 1.7 cm forward and 2.8 cm
+ * sideways and another 8.2 cm forward with its base down to 0.386 m; with it all four walk 4.5 .. 4.9 cm, within 2.2 mm sideways, base 0.398 .. 0.407 m).
+ * The latest selection starts at u = 0.48, the largest move of a foothold is 2.97 cm, and the smallest relative gap between the best and the second-best
+ * candidate is 1.7e-4 / 4.0e-3.
+ * tests/test_foothold_oracle.py holds the measured figures.
+ * wbc_foothold_params: a negative or non-finite value, u_max > 1, radius outside 0..4 or margin outside 0..2 gives WBC_E_INVALID.  The values travel as
+ * kernel arguments: nothing is uploaded, later calls use them; a cost map is as good as the w_step, w_slope and margin it was made with.  Not inside a
+ * stream capture (a captured graph keeps the values it was captured with).
+ * Stream rules as for the terrain calls: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at anything
+ * (wbc_terrain_cost_batch has no N); a NULL required pointer (terrain, cost, hold, latch included): WBC_E_INVALID; then the terrain struct's own checks;
+ * N > max_batch: WBC_E_CAPACITY -- all before the device is touched.  There is no single-robot host-pointer form, for the terrain calls' reason.
+ * Out of scope: the rollout kernels and wbc_rollout_*; wbc_multi_*; late touchdown; terrain sensing; smoothed normals; kinematic reachability of the
+ * chosen node (it lies at most radius cells, 4 at the most, from the gait rule's foothold in x and in y: the caller sizes radius * cell to the leg). */
+typedef struct wbc_foothold_params {
+  size_t struct_size;   /* sizeof(wbc_foothold_params) of the caller's build */
+  int radius;           /* R, cells: 0 .. 4; 0 = never select */
+  int margin;           /* the step term's neighbourhood, cells: 0 .. 2 */
+  double w_step, w_slope, w_dist;   /* >= 0 and finite; per m, per 1, per m (w_dist multiplies a squared distance) */
+  double cost_ok;       /* >= 0 and finite: a nearest node at most this costly is kept */
+  double u_max;         /* 0 .. 1: no selection starts later than this share of the swing */
+} wbc_foothold_params;
+void wbc_foothold_params_default(wbc_foothold_params* p);
+int wbc_solver_set_foothold_params(wbc_solver* s, const wbc_foothold_params* p);
+int wbc_terrain_cost_batch(wbc_solver* s, const wbc_terrain* terrain, void* cost /* out [n_tiles][ny][nx] */, void* stream);
+int wbc_foothold_select_batch(wbc_solver* s, const wbc_terrain* terrain, const void* cost, size_t N, const int* mask, void* swing /* in/out [36][N] */,
+                              void* hold /* in/out [8][N] */, int* latch /* in/out [N] */, void* stream);
+int wbc_gait_terrain_select_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact /* may be NULL */,
+                                  void* phase /* in/out [N] */, int* mask /* in/out [N] */, void* swing /* in/out [36][N] */,
+                                  int* events /* may be NULL, [N] */, const wbc_terrain* terrain, void* normals /* out [12][N] */,
+                                  void* height /* out [4][N] */, void* surf /* may be NULL */, const void* cost, void* hold /* in/out [8][N] */,
+                                  int* latch /* in/out [N] */, void* stream);
+int wbc_gait_estimated_terrain_select_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r,
+                                            const void* f_prev, void* normals /* in/out [12][N] */, int* contact /* in/out [N] */,
+                                            void* phase /* in/out [N] */, int* mask /* in/out [N] */, void* swing /* in/out [36][N] */,
+                                            int* events /* may be NULL, [N] */, void* f_est /* may be NULL */, const wbc_terrain* terrain,
+                                            void* height /* out [4][N] */, void* surf /* may be NULL */, const void* cost, void* hold /* in/out [8][N] */,
+                                            int* latch /* in/out [N] */, void* stream);
+
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
  * synchronises.  obs_integ/obs_r (host, nv each) are in/out and may be NULL when the observer is off. */

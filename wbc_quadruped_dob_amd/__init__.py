@@ -292,6 +292,15 @@ def lib():
             L.wbc_terrain_feet_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
             L.wbc_gait_terrain_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 13
             L.wbc_gait_estimated_terrain_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 17
+        # foothold selection: additive to ABI 10, detected by the symbols in the same way (_foothold_lib)
+        if hasattr(L, "wbc_gait_terrain_select_batch"):
+            L.wbc_foothold_params_default.argtypes = [C.c_void_p]
+            L.wbc_foothold_params_default.restype = None
+            L.wbc_solver_set_foothold_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_terrain_cost_batch.argtypes = [C.c_void_p] * 4
+            L.wbc_foothold_select_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
+            L.wbc_gait_terrain_select_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 16
+            L.wbc_gait_estimated_terrain_select_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 20
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -366,6 +375,14 @@ def _terrain_lib():
     L = lib()
     if not hasattr(L, "wbc_gait_terrain_batch"):
         raise RuntimeError("%s lacks the terrain entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+def _foothold_lib():
+    """lib(), for the foothold-selection calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_gait_terrain_select_batch"):
+        raise RuntimeError("%s lacks the foothold-selection entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     return L
 
 
@@ -516,6 +533,37 @@ class ContactParams(C.Structure):
 
     def as_dict(self):
         return dict(f_on=self.f_on, f_off=self.f_off, det_min=self.det_min)
+
+
+class FootholdParams(C.Structure):
+    """wbc_foothold_params: the weights of the terrain cost map and of the foothold search (include/wbc_hip.h, "Foothold selection")"""
+    _fields_ = [("struct_size", C.c_size_t), ("radius", C.c_int), ("margin", C.c_int), ("w_step", C.c_double), ("w_slope", C.c_double),
+                ("w_dist", C.c_double), ("cost_ok", C.c_double), ("u_max", C.c_double)]
+    _INTS, _REALS = ("radius", "margin"), ("w_step", "w_slope", "w_dist", "cost_ok", "u_max")
+
+    @staticmethod
+    def default():
+        p = FootholdParams()
+        _foothold_lib().wbc_foothold_params_default(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d):
+        """keys radius, margin (ints), w_step, w_slope, w_dist, cost_ok, u_max; missing keys keep the defaults"""
+        p = FootholdParams.default()
+        for k, val in d.items():
+            if k in FootholdParams._INTS:
+                if int(val) != val:
+                    raise ValueError("FootholdParams.%s is an integer" % k)
+                setattr(p, k, int(val))
+            elif k in FootholdParams._REALS:
+                setattr(p, k, float(val))
+            else:
+                raise KeyError("FootholdParams has no field %r" % k)
+        return p
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in FootholdParams._INTS + FootholdParams._REALS}
 
 
 class TerrainStruct(C.Structure):
@@ -1306,6 +1354,80 @@ class Solver:
                                                                self._terrain_arg(terrain, N), self._ptr(height, m.nf, N), self._ptr(surf, m.nf, N),
                                                                self._stream()), "wbc_gait_estimated_terrain_batch")
         return dict(contact=contact, phase=phase, mask=mask, swing=swing, events=events, f_est=f_est, normals=normals, height=height, surf=surf)
+
+    def set_foothold_params(self, p):
+        """p: FootholdParams or dict (see FootholdParams.from_dict): the weights of every later terrain_cost and selection call of this solver."""
+        if isinstance(p, dict):
+            p = FootholdParams.from_dict(p)
+        _check(_foothold_lib().wbc_solver_set_foothold_params(self._h, C.byref(p)), "wbc_solver_set_foothold_params")
+
+    def _foothold_ptrs(self, terrain, N, cost, hold, latch):
+        if cost is None or hold is None or latch is None:
+            raise ValueError("cost (terrain_cost()), hold ([8, N]) and latch (int32 [N]; store 0 before the first tick) are required tensors")
+        assert cost.dtype == self.tdtype and cost.is_contiguous() and cost.numel() == terrain.z.numel(), (cost.dtype, tuple(cost.shape))
+        return cost.data_ptr(), self._ptr(hold, 8, N), self._ptr(latch, 1, N, self.torch.int32)
+
+    def terrain_cost(self, terrain, cost=None):
+        """The cost of every node of a terrain (wbc_terrain_cost_batch), with the solver's foothold parameters: cost [n_tiles, ny, nx], laid out like
+        terrain.z.  One launch; make it once per map.  Returns cost."""
+        if cost is None:
+            cost = self.torch.empty_like(terrain.z)
+        assert cost.dtype == self.tdtype and cost.is_contiguous() and cost.shape == terrain.z.shape, (cost.dtype, tuple(cost.shape))
+        assert terrain.z.dtype == self.tdtype, (terrain.z.dtype, self.tdtype)
+        _check(_foothold_lib().wbc_terrain_cost_batch(self._h, C.byref(terrain.c), cost.data_ptr(), self._stream()), "wbc_terrain_cost_batch")
+        return cost
+
+    def foothold_select(self, terrain, cost, mask, swing, hold, latch):
+        """The selection law alone (wbc_foothold_select_batch) on mask and swing as a gait call left them: swing's p1_x, p1_y, hold [8, N] and latch
+        (int32 [N]) advance IN PLACE.  Returns dict(swing, hold, latch)."""
+        N = swing.shape[1]
+        cost_p, hold_p, latch_p = self._foothold_ptrs(terrain, N, cost, hold, latch)
+        _check(_foothold_lib().wbc_foothold_select_batch(self._h, self._terrain_arg(terrain, N), cost_p, N, self._ptr(mask, 1, N, self.torch.int32),
+                                                         self._ptr(swing, SWING_WORDS, N), hold_p, latch_p, self._stream()),
+               "wbc_foothold_select_batch")
+        return dict(swing=swing, hold=hold, latch=latch)
+
+    def gait_terrain_select(self, terrain, cost, hold, latch, q, v, cmd, phase, mask, swing, contact=None, events=None, normals=None, height=None,
+                            surf=None, want_surf=False):
+        """gait(), then foothold_select(), then terrain_feet(mask, swing), as one launch (wbc_gait_terrain_select_batch).  Returns dict(phase, mask,
+        swing, events, normals, height, surf, hold, latch)."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        normals, height, surf = self._terrain_out(N, normals, height, surf, want_surf)
+        _check(_foothold_lib().wbc_gait_terrain_select_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
+                                                             self._ptr(cmd, GAIT_CMD_WORDS, N), self._ptr(contact, 1, N, i32), self._ptr(phase, 1, N),
+                                                             self._ptr(mask, 1, N, i32), self._ptr(swing, SWING_WORDS, N),
+                                                             self._ptr(events, 1, N, i32), self._terrain_arg(terrain, N),
+                                                             self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(surf, m.nf, N),
+                                                             *self._foothold_ptrs(terrain, N, cost, hold, latch), self._stream()),
+               "wbc_gait_terrain_select_batch")
+        return dict(phase=phase, mask=mask, swing=swing, events=events, normals=normals, height=height, surf=surf, hold=hold, latch=latch)
+
+    def gait_estimated_terrain_select(self, terrain, cost, hold, latch, q, v, cmd, Jc, r, f_prev, normals, contact, phase, mask, swing, events=None,
+                                      f_est=None, want_f=False, height=None, surf=None, want_surf=False):
+        """gait_estimated(), then foothold_select(), then terrain_feet(mask, swing), as one launch (wbc_gait_estimated_terrain_select_batch).
+        normals [12, N] is IN/OUT as in gait_estimated_terrain().  Returns dict(contact, phase, mask, swing, events, f_est, normals, height, surf,
+        hold, latch)."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        if normals is None:
+            raise ValueError("normals is a required in/out tensor ([12, N]; store unit normals before the first call)")
+        if f_est is None and want_f:
+            f_est = self.empty(3 * m.nf, N)
+        _, height, surf = self._terrain_out(N, normals, height, surf, want_surf)
+        _check(_foothold_lib().wbc_gait_estimated_terrain_select_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N),
+                                                                       self._ptr(cmd, GAIT_CMD_WORDS, N),
+                                                                       *self._contact_in_ptrs(N, Jc, r, f_prev, normals, contact),
+                                                                       self._ptr(phase, 1, N), self._ptr(mask, 1, N, i32),
+                                                                       self._ptr(swing, SWING_WORDS, N), self._ptr(events, 1, N, i32),
+                                                                       self._ptr(f_est, 3 * m.nf, N), self._terrain_arg(terrain, N),
+                                                                       self._ptr(height, m.nf, N), self._ptr(surf, m.nf, N),
+                                                                       *self._foothold_ptrs(terrain, N, cost, hold, latch), self._stream()),
+               "wbc_gait_estimated_terrain_select_batch")
+        return dict(contact=contact, phase=phase, mask=mask, swing=swing, events=events, f_est=f_est, normals=normals, height=height, surf=surf,
+                    hold=hold, latch=latch)
 
     def compute_contact_estimate(self, Jc, r, f_prev, normals, contact=0):
         """Single-robot host-array form of contact_estimate (numpy float64, fp64 solvers; Jc [216] row-major 12 x 18): returns (contact, f_est[12],

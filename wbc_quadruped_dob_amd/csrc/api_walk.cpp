@@ -1,5 +1,5 @@
 // C-ABI (include/wbc_hip.h): the walking tick's families -- swing-foot references, the gait scheduler, the ground-contact plant and its stiction, contact
-// sensing from the observer's residual, the terrain heightfield.  Each: its parameters, the builder of its kernel argument, its one-launch batch calls.
+// sensing from the observer's residual, the terrain heightfield, foothold selection.  Each: its parameters, the builder of its kernel argument, its one-launch batch calls.
 #include "solver.hpp"
 
 using namespace wbc;
@@ -363,5 +363,112 @@ extern "C" int wbc_gait_estimated_terrain_batch(wbc_solver* s, size_t N, const v
     contact_io(a.e.c, s, Jc, r, f_prev, normals, contact, f_est, nullptr, nullptr);
     terrain_out(a.t, terrain, normals, height, surf);
     return k_gait_estimated_terrain<T>(L, dev_model<T>(s), a);
+  });
+}
+
+// ---- foothold selection: the weights, the cost map of a terrain, the law alone, and behind the two fused terrain calls as one launch each
+extern "C" void wbc_foothold_params_default(wbc_foothold_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->radius = 3; p->margin = 1;
+  p->w_step = 1.0; p->w_slope = 0.0078125; p->w_dist = 4.0; p->cost_ok = 0.00875; p->u_max = 0.75;   // how they were fixed: include/wbc_hip.h
+}
+
+extern "C" int wbc_solver_set_foothold_params(wbc_solver* s, const wbc_foothold_params* p) {
+  if (!s || !p) return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = check_struct_size(p, "wbc_foothold_params: struct_size too small (call wbc_foothold_params_default first)")) return rc;
+  if (p->radius < 0 || p->radius > 4) return fail(WBC_E_INVALID, "wbc_foothold_params: 0 <= radius <= 4");
+  if (p->margin < 0 || p->margin > 2) return fail(WBC_E_INVALID, "wbc_foothold_params: 0 <= margin <= 2");
+  if (const int rc = check_finite_nonneg({p->w_step, p->w_slope, p->w_dist, p->cost_ok, p->u_max},
+                                         "wbc_foothold_params: w_step, w_slope, w_dist, cost_ok, u_max must be finite and >= 0")) return rc;
+  if (p->u_max > 1) return fail(WBC_E_INVALID, "wbc_foothold_params: 0 <= u_max <= 1");
+  s->foothold = *p;
+  return WBC_OK;
+}
+
+template <class T>
+static void foothold_params(DevFootholdParams<T>& P, const wbc_solver* s) {
+  const wbc_foothold_params& f = s->foothold;
+  P.w_step = (T)f.w_step; P.w_slope = (T)f.w_slope; P.w_dist = (T)f.w_dist; P.cost_ok = (T)f.cost_ok; P.u_max = (T)f.u_max;
+  P.radius = f.radius; P.margin = f.margin;
+}
+// (behind terrain_check)
+template <class T>
+static void foothold_io(FootholdIO<T>& f, const wbc_solver* s, const wbc_terrain* t, const void* cost, void* hold, int* latch) {
+  f.cost = (const T*)cost; f.hold = (T*)hold; f.latch = latch; f.cell = (T)t->cell;
+  foothold_params(f.P, s);
+}
+
+extern "C" int wbc_terrain_cost_batch(wbc_solver* s, const wbc_terrain* terrain, void* cost, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (!terrain || !cost) return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = terrain_check(terrain)) return rc;
+  return launch_batch(s, 0, stream, "terrain cost", [&](auto scalar, const LaunchCtx& L) {   // (no batch: nothing to hold against max_batch)
+    using T = decltype(scalar);
+    TerrainCostArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    terrain_dev(a.g, terrain);
+    a.cost = (T*)cost;
+    a.nbx = ((unsigned)terrain->nx + 31u) / 32u; a.nby = ((unsigned)terrain->ny + 7u) / 8u;   // COST_TX, COST_TY of foothold.hip.hpp
+    foothold_params(a.P, s);
+    return k_terrain_cost<T>(L, a, (unsigned)terrain->n_tiles);
+  });
+}
+
+extern "C" int wbc_foothold_select_batch(wbc_solver* s, const wbc_terrain* terrain, const void* cost, size_t N, const int* mask, void* swing, void* hold,
+                                         int* latch, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!terrain || !cost || !mask || !swing || !hold || !latch) return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = terrain_check(terrain)) return rc;
+  return launch_batch(s, N, stream, "foothold select", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    FootholdSelectArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.mask = mask; a.swing = (T*)swing;
+    terrain_dev(a.g, terrain);
+    foothold_io(a.f, s, terrain, cost, hold, latch);
+    return k_foothold_select<T>(L, a);
+  });
+}
+
+extern "C" int wbc_gait_terrain_select_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const int* contact, void* phase,
+                                             int* mask, void* swing, int* events, const wbc_terrain* terrain, void* normals, void* height, void* surf,
+                                             const void* cost, void* hold, int* latch, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !phase || !mask || !swing || !terrain || !normals || !height || !cost || !hold || !latch)
+    return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = terrain_check(terrain)) return rc;
+  return launch_batch(s, N, stream, "gait terrain select", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GaitTerrainSelectArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    gait_args(a.g, s, N, q, v, cmd, contact, phase, mask, swing, events);
+    terrain_out(a.t, terrain, normals, height, surf);
+    foothold_io(a.f, s, terrain, cost, hold, latch);
+    return k_gait_terrain_select<T>(L, dev_model<T>(s), a);
+  });
+}
+
+extern "C" int wbc_gait_estimated_terrain_select_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* Jc,
+                                                       const void* r, const void* f_prev, void* normals, int* contact, void* phase, int* mask,
+                                                       void* swing, int* events, void* f_est, const wbc_terrain* terrain, void* height, void* surf,
+                                                       const void* cost, void* hold, int* latch, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !Jc || !r || !f_prev || !normals || !contact || !phase || !mask || !swing || !terrain || !height || !cost || !hold || !latch)
+    return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = terrain_check(terrain)) return rc;
+  return launch_batch(s, N, stream, "gait estimated terrain select", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GaitEstimatedTerrainSelectArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    gait_args(a.e.g, s, N, q, v, cmd, nullptr, phase, mask, swing, events);
+    contact_io(a.e.c, s, Jc, r, f_prev, normals, contact, f_est, nullptr, nullptr);
+    terrain_out(a.t, terrain, normals, height, surf);
+    foothold_io(a.f, s, terrain, cost, hold, latch);
+    return k_gait_estimated_terrain_select<T>(L, dev_model<T>(s), a);
   });
 }

@@ -305,6 +305,30 @@ template <class T> struct TerrainFeetArgs {   // terrain_feet_kernel
 };
 template <class T> struct GaitTerrainArgs { GaitArgs<T> g; TerrainOut<T> t; };                     // gait_terrain_kernel
 template <class T> struct GaitEstimatedTerrainArgs { GaitEstimatedArgs<T> e; TerrainOut<T> t; };   // gait_estimated_terrain_kernel: t.normals == e.c.normals
+// foothold selection (foothold.hip.hpp): the weights and what a call reads and writes -- BY VALUE like GroundIO (wbc_solver_set_foothold_params only
+// fills the solver's host copy).  cost is laid out like DevTerrain::z; cell is the terrain's, rounded to T
+template <class T> struct DevFootholdParams { T w_step, w_slope, w_dist, cost_ok, u_max; int radius, margin; };
+template <class T> struct FootholdIO {
+  const T* cost;   // [n_tiles][ny][nx]
+  T* hold;         // [8][N] in/out: rows 2k, 2k+1 = the latched x, y of foot k
+  int* latch;      // [N] in/out: in bit k = foot k is latched; out bits 0-3 the new latches, bit 4+k = foot k was selected this tick
+  T cell;
+  DevFootholdParams<T> P;
+};
+template <class T> struct TerrainCostArgs {   // terrain_cost_kernel: one workgroup per COST_TX x COST_TY nodes, nbx * nby of them per tile
+  DevTerrain<T> g;                            // (g.tile is not read)
+  T* cost;
+  unsigned nbx, nby;
+  DevFootholdParams<T> P;
+};
+template <class T> struct FootholdSelectArgs {   // foothold_select_kernel
+  size_t N;
+  const int* mask; T* swing;
+  DevTerrain<T> g;
+  FootholdIO<T> f;
+};
+template <class T> struct GaitTerrainSelectArgs { GaitArgs<T> g; TerrainOut<T> t; FootholdIO<T> f; };                     // gait_terrain_select_kernel
+template <class T> struct GaitEstimatedTerrainSelectArgs { GaitEstimatedArgs<T> e; TerrainOut<T> t; FootholdIO<T> f; };   // gait_estimated_terrain_select_kernel
 
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc

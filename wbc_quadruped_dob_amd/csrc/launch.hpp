@@ -126,5 +126,12 @@ template <class T> hipError_t k_terrain_sample(const LaunchCtx& L, const Terrain
 template <class T> hipError_t k_terrain_feet(const LaunchCtx& L, const DevModel<T>* model, const TerrainFeetArgs<T>& a);
 template <class T> hipError_t k_gait_terrain(const LaunchCtx& L, const DevModel<T>* model, const GaitTerrainArgs<T>& a);
 template <class T> hipError_t k_gait_estimated_terrain(const LaunchCtx& L, const DevModel<T>* model, const GaitEstimatedTerrainArgs<T>& a);
+// foothold selection (foothold.hip.hpp): terrain_cost_kernel<T> writes the cost of every node of a map (set-up time); foothold_select_kernel<T> is the
+// selection law alone on the mask and swing a gait call left; gait_terrain_select_kernel<T> / gait_estimated_terrain_select_kernel<T> are k_gait /
+// k_gait_estimated, then that law, then k_terrain_feet -- one launch each
+template <class T> hipError_t k_terrain_cost(const LaunchCtx& L, const TerrainCostArgs<T>& a, unsigned n_tiles);
+template <class T> hipError_t k_foothold_select(const LaunchCtx& L, const FootholdSelectArgs<T>& a);
+template <class T> hipError_t k_gait_terrain_select(const LaunchCtx& L, const DevModel<T>* model, const GaitTerrainSelectArgs<T>& a);
+template <class T> hipError_t k_gait_estimated_terrain_select(const LaunchCtx& L, const DevModel<T>* model, const GaitEstimatedTerrainSelectArgs<T>& a);
 
 }  // namespace wbc

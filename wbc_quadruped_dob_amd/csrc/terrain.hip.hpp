@@ -101,6 +101,22 @@ WBC_DEV void terrain_feet_tail(const TerrainOut<T>& t, V3<T> pf, int leg, unsign
   }
 }
 
+// terrain_feet_tail for a caller that holds the plan's (p1_x, p1_y) = swing words 9 leg + 3, 9 leg + 4 in registers (foothold.hip.hpp): the same
+// stores from the same bits, without the round trip through memory
+template <class T>
+WBC_DEV void terrain_feet_tail_at(const TerrainOut<T>& t, V3<T> pf, int leg, unsigned s32, size_t N, bool live, bool lifted, T* swing, T p1x, T p1y) {
+  const unsigned base = (t.g.tile ? (unsigned)t.g.tile[s32] : 0u) * t.g.tile_nodes;
+  const TerrainPlane<T> p = terrain_law<T>(t.g, base, pf.x, pf.y);
+  const T p1z = terrain_height<T>(t.g, base, p1x, p1y);
+  if (live) {
+    T* const no = t.normals + (size_t)(3 * leg) * N + s32;
+    no[0] = p.n.x; no[N] = p.n.y; no[2 * N] = p.n.z;
+    t.height[(size_t)leg * N + s32] = p.d;
+    if (t.surf) t.surf[(size_t)leg * N + s32] = p.zs;
+    if (lifted) swing[(size_t)(9 * leg + 5) * N + s32] = p1z;
+  }
+}
+
 // p_f(q) of the lane's leg: the text of gait_body.inc.hpp's position chain (its lines 18-62), over the same names
 template <class T>
 WBC_DEV V3<T> terrain_foot_point(const DevModel<T>* __restrict__ model, const T* cst, const T* q, unsigned long long jpack, int leg, unsigned s32, size_t N) {
