@@ -280,6 +280,23 @@ class QuadrupedWBC {
           "wbc_gait_estimated_terrain_select_batch");
   }
 
+  // Base state from leg odometry (wbc_hip.h, "Base state from leg odometry"): rows 0-2 of q_est, v_est estimated from the joints, the attitude, the gyro
+  // and the contact word; rows 0-2 of q and v are never read.  base [6][N] (the start state), anchor [12][N] and odo [N] (0 before the first tick) are
+  // caller-owned DEVICE buffers, advanced in place; normals and height are given together or both nullptr.  gaitEstimatedOdom is baseEstimate on the
+  // words as they arrive, then gaitEstimated on the estimated rows, one launch.  (The argument order of the C calls.)
+  void setOdomParams(const wbc_odom_params& p) { check(wbc_solver_set_odom_params(solver_, &p), "wbc_solver_set_odom_params"); }
+  void baseEstimate(size_t N, const void* q, const void* v, const int* contact, const int* mask, const void* normals, const void* height, void* base,
+                    void* anchor, int* odo, void* q_est, void* v_est, void* stream = nullptr) {
+    check(wbc_base_estimate_batch(solver_, N, q, v, contact, mask, normals, height, base, anchor, odo, q_est, v_est, stream), "wbc_base_estimate_batch");
+  }
+  void gaitEstimatedOdom(size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r, const void* f_prev, const void* normals,
+                         int* contact, void* phase, int* mask, void* swing, int* events /* may be nullptr */, void* f_est /* may be nullptr */,
+                         const void* height /* may be nullptr */, void* base, void* anchor, int* odo, void* q_est, void* v_est, void* stream = nullptr) {
+    check(wbc_gait_estimated_odom_batch(solver_, N, q, v, cmd, Jc, r, f_prev, normals, contact, phase, mask, swing, events, f_est, height, base, anchor,
+                                        odo, q_est, v_est, stream),
+          "wbc_gait_estimated_odom_batch");
+  }
+
   // Joint torque limits (wbc_hip.h, "Joint torque limits behind a tick").  effortLimits(): the URDF's <limit effort> per joint in jointNames() order,
   // HUGE_VAL where it gives none.  setTorqueLimits(): the limits the post-pass enforces (one value > 0 per joint; empty = back to the URDF's).
   std::vector<double> effortLimits() const {

@@ -867,6 +867,97 @@ int wbc_gait_estimated_terrain_select_batch(wbc_solver* s, size_t N, const void*
                                             void* height /* out [4][N] */, void* surf /* may be NULL */, const void* cost, void* hold /* in/out [8][N] */,
                                             int* latch /* in/out [N] */, void* stream);
 
+/* Base state from leg odometry: estimated rows 0-2 of q and v for the walking tick.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct,
+ * call, default or kernel output changes; detect it by these symbols).  Every launch of the tick reads the base position q[0..2] and the base linear
+ * velocity v[0..2]: on a simulator the plant's own, on a robot nobody's.  A controller has joint encoders, an attitude and a gyro (the quaternion rows
+ * of q, the angular rows of v) and the contact word it forms itself.  A loaded stance foot does not move, so it measures the trunk's velocity through
+ * its leg's Jacobian and the trunk's position through its leg's forward kinematics.  All arithmetic in the solver's scalar type T, per state.
+ * Inputs, device pointers, component-major:
+ *   q       [nq][N]   the sensor state: rows 3-6 the attitude, rows 7.. the joint angles.  Rows 0-2 are NEVER read.
+ *   v       [nv][N]   rows 3-5 the world angular velocity, rows 6.. the joint rates.  Rows 0-2 are NEVER read.
+ *   contact [N] int   bits 0-3: foot k senses ground (the estimated word of wbc_contact_estimate_batch, or the plant's)
+ *   mask    [N] int   bits 0-3: the previous tick's stance mask
+ *   normals [12][N], height [4][N]   the planes the step, the contact estimate and the ground calls read; given together, or both NULL
+ * Caller-owned state, advanced in place:
+ *   base    [6][N]    rows 0-2 p^, rows 3-5 v^.  The caller stores the start state.
+ *   anchor  [12][N]   rows 3k .. 3k+2 = the world point foot k stands on.  Needs no initial value.
+ *   odo     [N] int   in: bit k = foot k has an anchor (only bits 0-3 are read; the caller stores 0 before the first tick).
+ *                     out: bits 0-3 = the new anchors, bit 4+k = foot k was anchored THIS tick.
+ * Outputs: q_est [nq][N], v_est [nv][N]: rows 0-2 are p^ and v^, every other row is the input's bits.  They may be q and v themselves: the rows from
+ * 3 on are then not written.
+ * Per foot k, from the leg chain and velocity recursion of wbc_swing_reference_batch (d_k the foot point and vf_k its velocity in base coordinates
+ * with the base origin at rest, the base turning with R^T omega; the leg's joint columns come from the model, so joint orders that are not leg-major
+ * work):
+ *   lever_k = R d_k       u_k = R vf_k  (the foot's velocity relative to the base origin's)
+ *   S_k = contact bit k && mask bit k      cnt = |S|      inv[c] = T(1) / T(c)
+ * Velocity:  cnt > 0:  vm = -((u_0 + u_1) + (u_2 + u_3)) inv[cnt], the terms of feet outside S selected to exact 0 (not multiplied);
+ *                      v^ := v^ + a_v (vm - v^).       cnt = 0:  v^ is kept.
+ * Position:  p_pred = p^ + dt v^  (the new v^; dt is the solver's).  A = S && the in-bits of odo.
+ *            A != {}:  pm = ((x_0 + x_1) + (x_2 + x_3)) inv[|A|] with x_k = anchor_k - lever_k (exact 0 outside A);  p^ := p_pred + a_p (pm - p_pred).
+ *            A == {}:  p^ := p_pred.
+ * Anchors:   k in S without an anchor:  x = p^ + lever_k (the new p^);  with planes, x := x - n_k (n_k . x - height_k);  anchor_k := x, bit k := 1,
+ *                                       bit 4+k := 1
+ *            k in S and A:              its three anchor words are untouched, bit for bit; bit k stays 1
+ *            k not in S:                bit k := 0, its anchor words untouched (and never read: they may hold anything)
+ * odo, the copied rows and every untouched word are EXACT.  p^, v^ and new anchors are exact only to rounding: the compiler may contract products.
+ *   wbc_base_estimate_batch        the law alone
+ *   wbc_gait_estimated_odom_batch  wbc_gait_estimated_batch's arguments + height (may be NULL: no planes), base, anchor, odo, q_est, v_est: ONE launch
+ *                                  that evaluates (1) this law on contact and mask AS LOADED -- the previous tick's words, read before anything
+ *                                  overwrites them -- (2) the contact law, (3) the gait rule on the ESTIMATED base rows, held in registers.  Its
+ *                                  outputs are those of wbc_base_estimate_batch followed by wbc_gait_estimated_batch(q_est, v_est).
+ *   wbc_compute_base_estimate      the single-robot, host-pointer, fp64 form (q[19], v[18], the two words, normals[12] and height[4] or both NULL in;
+ *                                  base[6], anchor[12], odo[1] in/out; q_est[19], v_est[18] out).  Synchronises.
+ * The walking tick becomes
+ *   gait_estimated_odom -> reference_swing(q_est, v_est) -> step(q_est, v_est; observer on) -> integrate_ground[_stick](the true q, v)
+ * still four launches with no host work between them, and none of the first three reads a base row of the plant's state.
+ * The defaults
+ *   a_v = 2^-3,  a_p = 2^-2
+ * were fixed on the CPU with the numpy restatement of this law (tests/odom_ref.py) in the walking loop of the stiction plant (tests/stick_ref.py's
+ * walk_case: 4 robots, 512 ticks of 2^-10 s, a 15 mm bump under one foot, command 0.1 m/s), the controller links given q_est, v_est and the plant the
+ * truth.  The ground is a penalty spring: a loaded foot sinks m g / (2 k_n), about 5 mm, and moves while it does, so raw odometry (a_v = a_p = 1) is
+ * noisy and an anchor taken where the foot touched leaves z one penetration depth low at every step; the blend and the drop of a new anchor onto
+ * the foot's known plane remove both.  What remains is a bounded bias of about one penetration depth: the estimate reads high, so the trunk rides a
+ * few mm low.  The vertical velocity stays rough (this law has no accelerometer).
+ * Measured there (every QP status 0 in every loop but where said; the loop on the true state walks 4.95 .. 5.12 cm and ends at base z 0.4024 .. 0.4033 m):
+ *   a_v / a_p       forward travel       base z at the end      worst |p^ - p| x / y / z     rms v error x / y / z
+ *   2^-3 / 2^-2     3.47 .. 5.41 cm      0.3937 .. 0.4103 m     31.3 / 5.7 / 8.9 mm          0.063 / 0.033 / 0.063 m/s     (the defaults)
+ *   2^-4 / 2^-2     3.16 .. 4.22 cm      0.3953 .. 0.4102 m     28.7 / 5.5 / 9.3 mm          0.059 / 0.033 / 0.069
+ *   2^-2 / 2^-2     3.69 .. 5.37 cm      0.3944 .. 0.4101 m     34.9 / 6.6 / 8.4 mm          0.069 / 0.034 / 0.073; worst v error 0.72 m/s (defaults: 0.38)
+ *   2^-3 / 2^-1     3.51 .. 5.57 cm      0.3935 .. 0.4108 m     33.1 / 6.5 / 8.9 mm          0.063 / 0.032 / 0.063
+ *   2^-3 / 2^-3     3.65 .. 5.32 cm      0.3940 .. 0.4096 m     29.4 / 5.4 / 8.8 mm          0.062 / 0.032 / 0.063
+ *   1 / 1 (raw)     17.9 .. 25.4 cm      0.495 .. 0.527 m       114 / 123 / 608 mm           3.1 / 3.3 / 4.3; did NOT pass: the estimate runs away (v error up to 105 m/s)
+ *   2^-3 / 2^-2 without planes:  0.74 .. 4.27 cm, z^ reads 15 .. 19 mm high at the end and keeps the penetration of every step: did NOT pass
+ * No dyadic neighbour of the start values is better in travel and in error at once, so they stay.  The x error is larger than the y and z errors because
+ * it is taken at touchdowns: the foot that meets the 15 mm bump lands early, carries 40 N and slides at 0.5 .. 0.2 m/s for thirty ticks while both
+ * words call it down, and the estimated word of a foot the schedule has just put down carries its planned force, so its bit is set a tick or two
+ * before the foot is.  With the plant's own word in place of the estimated one the figures are 3.02 .. 5.57 cm, 38.0 / 5.7 / 7.7 mm.
+ * Both gains are dyadic, so the blends' products are exact.  tests/test_odom_oracle.py holds the measured figures.
+ * wbc_odom_params: a_v outside (0, 1], a_p outside [0, 1] or a non-finite value gives WBC_E_INVALID.  The values travel as kernel arguments: nothing is
+ * uploaded, later calls use them.  Not inside a stream capture (a captured graph keeps the values it was captured with).
+ * Stream rules as for the contact calls: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at the buffers; a
+ * NULL required pointer, or normals without height (or the reverse): WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY -- all before the device is touched.
+ * Out of scope: an accelerometer or a Kalman covariance; attitude estimation; compensating the penetration bias from f_est; the terrain and
+ * foothold-select fused variants (a caller there runs wbc_base_estimate_batch as a fifth launch); the rollout kernels and wbc_rollout_*; wbc_multi_*. */
+typedef struct wbc_odom_params {
+  size_t struct_size;   /* sizeof(wbc_odom_params) of the caller's build */
+  double a_v;           /* the velocity blend: 0 < a_v <= 1 */
+  double a_p;           /* the position blend: 0 <= a_p <= 1 (0 = dead reckoning on v^) */
+} wbc_odom_params;
+void wbc_odom_params_default(wbc_odom_params* p);
+int wbc_solver_set_odom_params(wbc_solver* s, const wbc_odom_params* p);
+int wbc_base_estimate_batch(wbc_solver* s, size_t N, const void* q, const void* v, const int* contact, const int* mask,
+                            const void* normals /* may be NULL with height */, const void* height /* may be NULL with normals */,
+                            void* base /* in/out [6][N] */, void* anchor /* in/out [12][N] */, int* odo /* in/out [N] */, void* q_est /* out [nq][N] */,
+                            void* v_est /* out [nv][N] */, void* stream);
+int wbc_gait_estimated_odom_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r,
+                                  const void* f_prev, const void* normals, int* contact /* in/out [N] */, void* phase /* in/out [N] */,
+                                  int* mask /* in/out [N] */, void* swing /* in/out [36][N] */, int* events /* may be NULL, [N] */,
+                                  void* f_est /* may be NULL */, const void* height /* may be NULL */, void* base /* in/out [6][N] */,
+                                  void* anchor /* in/out [12][N] */, int* odo /* in/out [N] */, void* q_est /* out [nq][N] */,
+                                  void* v_est /* out [nv][N] */, void* stream);
+int wbc_compute_base_estimate(wbc_solver* s, const double* q, const double* v, int contact, int mask, const double* normals /* may be NULL with height */,
+                              const double* height, double* base, double* anchor, int* odo, double* q_est, double* v_est);
+
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
  * synchronises.  obs_integ/obs_r (host, nv each) are in/out and may be NULL when the observer is off. */

@@ -301,6 +301,14 @@ def lib():
             L.wbc_foothold_select_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
             L.wbc_gait_terrain_select_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 16
             L.wbc_gait_estimated_terrain_select_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 20
+        # base state from leg odometry: additive to ABI 10, detected by the symbols in the same way (_odom_lib)
+        if hasattr(L, "wbc_gait_estimated_odom_batch"):
+            L.wbc_odom_params_default.argtypes = [C.c_void_p]
+            L.wbc_odom_params_default.restype = None
+            L.wbc_solver_set_odom_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_base_estimate_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 12
+            L.wbc_gait_estimated_odom_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 20
+            L.wbc_compute_base_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -383,6 +391,14 @@ def _foothold_lib():
     L = lib()
     if not hasattr(L, "wbc_gait_terrain_select_batch"):
         raise RuntimeError("%s lacks the foothold-selection entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+def _odom_lib():
+    """lib(), for the base-estimate calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_gait_estimated_odom_batch"):
+        raise RuntimeError("%s lacks the base-estimate entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     return L
 
 
@@ -533,6 +549,30 @@ class ContactParams(C.Structure):
 
     def as_dict(self):
         return dict(f_on=self.f_on, f_off=self.f_off, det_min=self.det_min)
+
+
+class OdomParams(C.Structure):
+    """wbc_odom_params: the blend gains of the base estimate (include/wbc_hip.h, "Base state from leg odometry")"""
+    _fields_ = [("struct_size", C.c_size_t), ("a_v", C.c_double), ("a_p", C.c_double)]
+
+    @staticmethod
+    def default():
+        p = OdomParams()
+        _odom_lib().wbc_odom_params_default(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d):
+        """keys a_v, a_p; missing keys keep the defaults"""
+        p = OdomParams.default()
+        for k, val in d.items():
+            if k not in ("a_v", "a_p"):
+                raise KeyError("OdomParams has no field %r" % k)
+            setattr(p, k, float(val))
+        return p
+
+    def as_dict(self):
+        return dict(a_v=self.a_v, a_p=self.a_p)
 
 
 class FootholdParams(C.Structure):
@@ -1428,6 +1468,69 @@ class Solver:
                "wbc_gait_estimated_terrain_select_batch")
         return dict(contact=contact, phase=phase, mask=mask, swing=swing, events=events, f_est=f_est, normals=normals, height=height, surf=surf,
                     hold=hold, latch=latch)
+
+    def set_odom_params(self, p):
+        """p: OdomParams or dict (see OdomParams.from_dict): the blend gains of every later base-estimate call of this solver."""
+        if isinstance(p, dict):
+            p = OdomParams.from_dict(p)
+        _check(_odom_lib().wbc_solver_set_odom_params(self._h, C.byref(p)), "wbc_solver_set_odom_params")
+
+    def _odom_ptrs(self, N, q, v, normals, height, base, anchor, odo, q_est, v_est):
+        """-> (height, base, anchor, odo, q_est, v_est pointers, q_est, v_est); q_est / v_est None: fresh tensors (pass q, v themselves to write
+        rows 0-2 in place)"""
+        m = self.model
+        if base is None or anchor is None or odo is None:
+            raise ValueError("base ([6, N]; store the start state), anchor ([12, N]) and odo (int32 [N]; store 0 before the first tick) are required tensors")
+        q_est = self.empty(m.nq, N) if q_est is None else q_est
+        v_est = self.empty(m.nv, N) if v_est is None else v_est
+        return (self._ptr(height, m.nf, N), self._ptr(base, 6, N), self._ptr(anchor, 3 * m.nf, N), self._ptr(odo, 1, N, self.torch.int32),
+                self._ptr(q_est, m.nq, N), self._ptr(v_est, m.nv, N), q_est, v_est)
+
+    def base_estimate(self, q, v, contact, mask, base, anchor, odo, normals=None, height=None, q_est=None, v_est=None):
+        """Base position and linear velocity from leg odometry (wbc_base_estimate_batch).  Rows 0-2 of q and v are never read.  contact, mask
+        (int32 [N]): a foot is trusted where both have its bit.  normals [12, N] and height [4, N]: given together or not at all.  base [6, N],
+        anchor [12, N] and odo (int32 [N]) advance IN PLACE.  q_est, v_est: rows 0-2 the estimate, the other rows copies; they may be q and v
+        themselves.  Returns dict(base, anchor, odo, q_est, v_est)."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        hp, bp, ap, op, qp, vp, q_est, v_est = self._odom_ptrs(N, q, v, normals, height, base, anchor, odo, q_est, v_est)
+        _check(_odom_lib().wbc_base_estimate_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(contact, 1, N, i32),
+                                                   self._ptr(mask, 1, N, i32), self._ptr(normals, 3 * m.nf, N), hp, bp, ap, op, qp, vp,
+                                                   self._stream()), "wbc_base_estimate_batch")
+        return dict(base=base, anchor=anchor, odo=odo, q_est=q_est, v_est=v_est)
+
+    def gait_estimated_odom(self, q, v, cmd, Jc, r, f_prev, normals, contact, phase, mask, swing, base, anchor, odo, height=None, q_est=None,
+                            v_est=None, events=None, f_est=None, want_f=False):
+        """base_estimate() on contact and mask as they arrive (the previous tick's), then gait_estimated(q_est, v_est), as one launch
+        (wbc_gait_estimated_odom_batch).  contact, phase, mask, swing, base, anchor and odo advance IN PLACE.  height None: new anchors are not
+        dropped onto the planes.  Returns dict(contact, phase, mask, swing, events, f_est, base, anchor, odo, q_est, v_est)."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        if f_est is None and want_f:
+            f_est = self.empty(3 * m.nf, N)
+        hp, bp, ap, op, qp, vp, q_est, v_est = self._odom_ptrs(N, q, v, normals, height, base, anchor, odo, q_est, v_est)
+        _check(_odom_lib().wbc_gait_estimated_odom_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(cmd, GAIT_CMD_WORDS, N),
+                                                         *self._contact_in_ptrs(N, Jc, r, f_prev, normals, contact), self._ptr(phase, 1, N),
+                                                         self._ptr(mask, 1, N, i32), self._ptr(swing, SWING_WORDS, N), self._ptr(events, 1, N, i32),
+                                                         self._ptr(f_est, 3 * m.nf, N), hp, bp, ap, op, qp, vp, self._stream()),
+               "wbc_gait_estimated_odom_batch")
+        return dict(contact=contact, phase=phase, mask=mask, swing=swing, events=events, f_est=f_est, base=base, anchor=anchor, odo=odo,
+                    q_est=q_est, v_est=v_est)
+
+    def compute_base_estimate(self, q, v, contact, mask, base, anchor, odo=0, normals=None, height=None):
+        """Single-robot host-array form of base_estimate (numpy float64, fp64 solvers): returns (base[6], anchor[12], odo, q_est[19], v_est[18]);
+        the inputs are not modified."""
+        import numpy as np
+        arr = lambda a, n: None if a is None else np.ascontiguousarray(np.asarray(a, np.float64).reshape(n))
+        q, v, normals, height = arr(q, 19), arr(v, 18), arr(normals, 12), arr(height, 4)
+        base, anchor = arr(base, 6).copy(), arr(anchor, 12).copy()
+        qe, ve, ow = np.empty(19), np.empty(18), C.c_int(int(odo))
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _check(_odom_lib().wbc_compute_base_estimate(self._h, p(q), p(v), int(contact), int(mask), p(normals), p(height), p(base), p(anchor),
+                                                     C.byref(ow), p(qe), p(ve)), "wbc_compute_base_estimate")
+        return base, anchor, ow.value, qe, ve
 
     def compute_contact_estimate(self, Jc, r, f_prev, normals, contact=0):
         """Single-robot host-array form of contact_estimate (numpy float64, fp64 solvers; Jc [216] row-major 12 x 18): returns (contact, f_est[12],

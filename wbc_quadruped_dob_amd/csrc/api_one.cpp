@@ -248,3 +248,28 @@ extern "C" int wbc_compute_contact_estimate(wbc_solver* s, const double* Jc, con
   if (singular) *singular = hi[1];
   return WBC_OK;
 }
+
+extern "C" int wbc_compute_base_estimate(wbc_solver* s, const double* q, const double* v, int contact, int mask, const double* normals,
+                                         const double* height, double* base, double* anchor, int* odo, double* q_est, double* v_est) {
+  if (!s || !q || !v || !base || !anchor || !odo || !q_est || !v_est) return fail(WBC_E_INVALID, "null argument");
+  if ((normals == nullptr) != (height == nullptr)) return fail(WBC_E_INVALID, "normals and height are given together or both NULL");
+  if (s->dtype != WBC_F64) return fail(WBC_E_INVALID, "wbc_compute_base_estimate: fp64 solvers only");
+  ON_DEVICE(s);
+  const int oq = 0, ov = 19, on = 37, oh = 49, ob = 53, oa = 59, oqe = 71, ove = 90;   // q v normals height | base anchor q_est v_est, and three ints: contact, mask, odo
+  double h[ove + 18];
+  static_assert(ove + 18 <= STAGE_ONE_DOUBLES, "the staging block holds this call");
+  std::memset(h, 0, sizeof(h));
+  std::memcpy(h + oq, q, 19 * sizeof(double)); std::memcpy(h + ov, v, 18 * sizeof(double));
+  if (normals) { std::memcpy(h + on, normals, 12 * sizeof(double)); std::memcpy(h + oh, height, 4 * sizeof(double)); }
+  std::memcpy(h + ob, base, 6 * sizeof(double)); std::memcpy(h + oa, anchor, 12 * sizeof(double));
+  int hi[3] = {contact, mask, *odo};
+  const int rc = stage_one(s, h, oqe, hi, 3, ob, ove + 18 - ob, 3, [&](double* d, int* di) {
+    return wbc_base_estimate_batch(s, 1, d + oq, d + ov, di, di + 1, normals ? d + on : nullptr, normals ? d + oh : nullptr, d + ob, d + oa, di + 2,
+                                   d + oqe, d + ove, nullptr);
+  });
+  if (rc) return rc;
+  std::memcpy(base, h + ob, 6 * sizeof(double)); std::memcpy(anchor, h + oa, 12 * sizeof(double));
+  std::memcpy(q_est, h + oqe, 19 * sizeof(double)); std::memcpy(v_est, h + ove, 18 * sizeof(double));
+  *odo = hi[2];
+  return WBC_OK;
+}

@@ -1,5 +1,5 @@
 // C-ABI (include/wbc_hip.h): the walking tick's families -- swing-foot references, the gait scheduler, the ground-contact plant and its stiction, contact
-// sensing from the observer's residual, the terrain heightfield, foothold selection.  Each: its parameters, the builder of its kernel argument, its one-launch batch calls.
+// sensing from the observer's residual, the terrain heightfield, foothold selection, the base state from leg odometry.  Each: its parameters, the builder of its kernel argument, its one-launch batch calls.
 #include "solver.hpp"
 
 using namespace wbc;
@@ -470,5 +470,65 @@ extern "C" int wbc_gait_estimated_terrain_select_batch(wbc_solver* s, size_t N, 
     terrain_out(a.t, terrain, normals, height, surf);
     foothold_io(a.f, s, terrain, cost, hold, latch);
     return k_gait_estimated_terrain_select<T>(L, dev_model<T>(s), a);
+  });
+}
+
+// ---- base state from leg odometry: the gains, the law alone, the law + the contact estimate + the gait scheduler as one launch
+extern "C" void wbc_odom_params_default(wbc_odom_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->a_v = 0.125; p->a_p = 0.25;   // how they were fixed: include/wbc_hip.h
+}
+
+extern "C" int wbc_solver_set_odom_params(wbc_solver* s, const wbc_odom_params* p) {
+  if (!s || !p) return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = check_struct_size(p, "wbc_odom_params: struct_size too small (call wbc_odom_params_default first)")) return rc;
+  if (!(p->a_v > 0 && p->a_v <= 1)) return fail(WBC_E_INVALID, "wbc_odom_params: 0 < a_v <= 1");
+  if (!(p->a_p >= 0 && p->a_p <= 1)) return fail(WBC_E_INVALID, "wbc_odom_params: 0 <= a_p <= 1");
+  s->odom = *p;
+  return WBC_OK;
+}
+
+template <class T>
+static void odom_io(OdomIO<T>& o, const wbc_solver* s, const int* contact, const int* mask, const void* normals, const void* height, void* base,
+                    void* anchor, int* odo, void* q_est, void* v_est) {
+  o.contact = contact; o.mask = mask; o.normals = (const T*)normals; o.height = (const T*)height;
+  o.base = (T*)base; o.anchor = (T*)anchor; o.odo = odo; o.q_est = (T*)q_est; o.v_est = (T*)v_est;
+  o.a_v = (T)s->odom.a_v; o.a_p = (T)s->odom.a_p; o.dt = (T)s->params.dt;
+}
+
+extern "C" int wbc_base_estimate_batch(wbc_solver* s, size_t N, const void* q, const void* v, const int* contact, const int* mask, const void* normals,
+                                       const void* height, void* base, void* anchor, int* odo, void* q_est, void* v_est, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !contact || !mask || !base || !anchor || !odo || !q_est || !v_est) return fail(WBC_E_INVALID, "null argument");
+  if ((normals == nullptr) != (height == nullptr)) return fail(WBC_E_INVALID, "normals and height are given together or both NULL");
+  return launch_batch(s, N, stream, "base estimate", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    OdomArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.jpack = s->jpack;
+    odom_io(a.o, s, contact, mask, normals, height, base, anchor, odo, q_est, v_est);
+    return k_base_estimate<T>(L, dev_model<T>(s), a);
+  });
+}
+
+extern "C" int wbc_gait_estimated_odom_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* Jc, const void* r,
+                                             const void* f_prev, const void* normals, int* contact, void* phase, int* mask, void* swing, int* events,
+                                             void* f_est, const void* height, void* base, void* anchor, int* odo, void* q_est, void* v_est,
+                                             void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !Jc || !r || !f_prev || !normals || !contact || !phase || !mask || !swing || !base || !anchor || !odo || !q_est || !v_est)
+    return fail(WBC_E_INVALID, "null argument");
+  return launch_batch(s, N, stream, "gait estimated odom", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    GaitEstimatedOdomArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    gait_args(a.e.g, s, N, q, v, cmd, nullptr, phase, mask, swing, events);
+    contact_io(a.e.c, s, Jc, r, f_prev, normals, contact, f_est, nullptr, nullptr);
+    odom_io(a.o, s, contact, mask, normals, height, base, anchor, odo, q_est, v_est);
+    return k_gait_estimated_odom<T>(L, dev_model<T>(s), a);
   });
 }

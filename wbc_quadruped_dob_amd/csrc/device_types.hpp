@@ -329,6 +329,25 @@ template <class T> struct FootholdSelectArgs {   // foothold_select_kernel
 };
 template <class T> struct GaitTerrainSelectArgs { GaitArgs<T> g; TerrainOut<T> t; FootholdIO<T> f; };                     // gait_terrain_select_kernel
 template <class T> struct GaitEstimatedTerrainSelectArgs { GaitEstimatedArgs<T> e; TerrainOut<T> t; FootholdIO<T> f; };   // gait_estimated_terrain_select_kernel
+// base state from leg odometry (odom.hip.hpp): the gains and what a call reads and writes -- BY VALUE like GroundIO (wbc_solver_set_odom_params only
+// fills the solver's host copy).  dt is the solver's
+template <class T> struct OdomIO {
+  const int* contact; const int* mask;   // [N], [N]: the words the law trusts a foot by (bits 0-3)
+  const T* normals; const T* height;     // [12][N], [4][N]; height null = no planes (normals is then not read)
+  T* base;      // [6][N] in/out: rows 0-2 the position estimate, rows 3-5 the velocity estimate
+  T* anchor;    // [12][N] in/out: rows 3k .. 3k+2 = the world point foot k stands on
+  int* odo;     // [N] in/out: in bit k = foot k has an anchor; out bits 0-3 the new anchors, bit 4+k = foot k was anchored this tick
+  T* q_est; T* v_est;   // [nq][N], [nv][N]; rows 3 .. are not written where q_est == q (v_est == v)
+  T a_v, a_p, dt;
+};
+template <class T> struct OdomArgs {   // base_estimate_kernel
+  size_t N;
+  const T* q; const T* v;      // rows 0-2 are never read
+  unsigned long long jpack;    // see SweepArgs::jpack
+  OdomIO<T> o;
+};
+// gait_estimated_odom_kernel: o.contact == e.c.contact, o.mask == e.g.mask, o.normals == e.c.normals; rows 0-2 of e.g.q, e.g.v are never read
+template <class T> struct GaitEstimatedOdomArgs { GaitEstimatedArgs<T> e; OdomIO<T> o; };
 
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc

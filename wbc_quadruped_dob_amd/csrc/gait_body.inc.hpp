@@ -2,9 +2,22 @@
 // sensed word in the same launch.  As a function template over "the word is given" the body moved gait_kernel's register allocation; as text,
 // gait_kernel assembles as before.  The includer provides `model` (const DevModel<T>*), `a` (GaitArgs<T>, or a reference to one) and the macro
 // GAIT_SENSED_WORD: the expression for the four sensed bits of state s32 (gait_kernel: a.contact ? a.contact[s32] : 0).
+// Optional hooks of the same kind, for an includer that holds the base state in registers (gait_estimated_odom_kernel, odom.hip.hpp); left
+// undefined they are today's text:  GAIT_BASE_Q(c) row c of q for c = 0 .. 6,  GAIT_BASE_V(c) row c of v for c = 0, 1,  GAIT_CST_STAGED the
+// includer has declared and staged `cst` itself.
+#ifndef GAIT_BASE_Q
+#define GAIT_BASE_Q(c) ROWI(a.q, c)
+#define GAIT_BASE_Q_DEFAULTED_
+#endif
+#ifndef GAIT_BASE_V
+#define GAIT_BASE_V(c) ROWI(a.v, c)
+#define GAIT_BASE_V_DEFAULTED_
+#endif
+#ifndef GAIT_CST_STAGED
   __shared__ T cst[CST_WORDS];
   for (int i = threadIdx.x; i < CST_WORDS; i += blockDim.x) cst[i] = model->cst[i];
   __syncthreads();
+#endif
   WBC_LAUNDERED_TID(tx);
   const size_t N = a.N;
   const LegLane lane_ = leg_lane<16>(tx, N);   // lanes beyond the batch recompute its last state and store nothing
@@ -17,8 +30,8 @@
   const int sensed = GAIT_SENSED_WORD;
   T qb[7];
 #pragma unroll
-  for (int c = 0; c < 7; ++c) qb[c] = ROWI(a.q, c);
-  const T vx = ROWI(a.v, 0), vy = ROWI(a.v, 1);
+  for (int c = 0; c < 7; ++c) qb[c] = GAIT_BASE_Q(c);
+  const T vx = GAIT_BASE_V(0), vy = GAIT_BASE_V(1);
   const T cvx = ROWI(a.cmd, 0), cvy = ROWI(a.cmd, 1), wz = ROWI(a.cmd, 2), zg = ROWI(a.cmd, 3);
   int jx[3];
   jidx_of_leg(model, a.jpack, leg, jx);
@@ -102,3 +115,11 @@
     a.mask[s32] = gait_gather(bm, st);
     if (a.events) a.events[s32] = gait_gather(bl, st) | (gait_gather(bt, st) << 4);
   }
+#ifdef GAIT_BASE_Q_DEFAULTED_
+#undef GAIT_BASE_Q
+#undef GAIT_BASE_Q_DEFAULTED_
+#endif
+#ifdef GAIT_BASE_V_DEFAULTED_
+#undef GAIT_BASE_V
+#undef GAIT_BASE_V_DEFAULTED_
+#endif

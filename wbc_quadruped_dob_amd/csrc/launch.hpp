@@ -133,5 +133,9 @@ template <class T> hipError_t k_terrain_cost(const LaunchCtx& L, const TerrainCo
 template <class T> hipError_t k_foothold_select(const LaunchCtx& L, const FootholdSelectArgs<T>& a);
 template <class T> hipError_t k_gait_terrain_select(const LaunchCtx& L, const DevModel<T>* model, const GaitTerrainSelectArgs<T>& a);
 template <class T> hipError_t k_gait_estimated_terrain_select(const LaunchCtx& L, const DevModel<T>* model, const GaitEstimatedTerrainSelectArgs<T>& a);
+// base state from leg odometry (odom.hip.hpp): base_estimate_kernel<T> is the law alone (base, anchor, odo in place; q_est, v_est); gait_estimated_odom_kernel<T>
+// is that law, then k_gait_estimated with the estimated base rows handed over in registers -- one launch
+template <class T> hipError_t k_base_estimate(const LaunchCtx& L, const DevModel<T>* model, const OdomArgs<T>& a);
+template <class T> hipError_t k_gait_estimated_odom(const LaunchCtx& L, const DevModel<T>* model, const GaitEstimatedOdomArgs<T>& a);
 
 }  // namespace wbc

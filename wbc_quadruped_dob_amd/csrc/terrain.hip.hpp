@@ -117,7 +117,7 @@ WBC_DEV void terrain_feet_tail_at(const TerrainOut<T>& t, V3<T> pf, int leg, uns
   }
 }
 
-// p_f(q) of the lane's leg: the text of gait_body.inc.hpp's position chain (its lines 18-62), over the same names
+// p_f(q) of the lane's leg: the text of gait_body.inc.hpp's position chain (its lines 32-76), over the same names
 template <class T>
 WBC_DEV V3<T> terrain_foot_point(const DevModel<T>* __restrict__ model, const T* cst, const T* q, unsigned long long jpack, int leg, unsigned s32, size_t N) {
   T qb[7];
