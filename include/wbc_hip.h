@@ -741,6 +741,11 @@ int wbc_compute_contact_estimate(wbc_solver* s, const double* Jc, const double* 
  *                              untouched bit for bit.  The rule is idempotent, so it is the same for retarget 0 and 1.
  *   wbc_gait_terrain_batch     wbc_gait_batch's arguments + terrain, normals, height, surf: ONE launch whose outputs are those of wbc_gait_batch followed
  *                              by wbc_terrain_feet_batch(mask, swing = what the gait call left).  cmd row 3 is then dead for lifted feet.
+ *                              phase, mask, events and every swing word but p0 are the two launches' bit for bit (p1_z too: it is sampled at p1_x,
+ *                              p1_y as read back from memory).  normals, height, surf and the p0 of a foot that lifts off in this call descend from
+ *                              p_f(q), and the compiler contracts the leg chain differently in the three kernels: they agree to rounding, not to
+ *                              the bit (on a walking loop's states p0 has so far come out equal; on states with joints over several turns and
+ *                              attitudes over the sphere about one lifting foot in ten differs in its last bits -- tests/test_gpu_walk_edges.py).
  *   wbc_gait_estimated_terrain_batch   the same behind wbc_gait_estimated_batch.  normals is IN/OUT: the contact law reads the previous tick's
  *                              planes, then they are overwritten with this tick's (before the first tick the caller stores any unit normals).
  * The walking tick stays at four launches with no host work between them:
@@ -813,7 +818,8 @@ int wbc_gait_estimated_terrain_batch(wbc_solver* s, size_t N, const void* q, con
  *   wbc_gait_terrain_select_batch           wbc_gait_terrain_batch's arguments + cost, hold, latch: ONE launch whose outputs are those of wbc_gait_batch,
  *                                           then wbc_foothold_select_batch, then wbc_terrain_feet_batch(mask, swing) -- bit for bit, but for normals,
  *                                           height and surf, which are wbc_gait_terrain_batch's own bits (they agree with wbc_terrain_feet_batch's
- *                                           to rounding, as that call's do).  With radius = 0 and no latch bit set its other outputs are
+ *                                           to rounding, as that call's do), and for the p0 of a foot that lifts off in this call, which descends
+ *                                           from p_f(q) as they do and agrees with wbc_gait_batch's to rounding.  With radius = 0 and no latch bit set its other outputs are
  *                                           wbc_gait_terrain_batch's bit for bit.
  *   wbc_gait_estimated_terrain_select_batch the same behind wbc_gait_estimated_batch
  * The walking tick stays at four launches with no host work between them:
@@ -873,7 +879,8 @@ int wbc_gait_estimated_terrain_select_batch(wbc_solver* s, size_t N, const void*
  * of q, the angular rows of v) and the contact word it forms itself.  A loaded stance foot does not move, so it measures the trunk's velocity through
  * its leg's Jacobian and the trunk's position through its leg's forward kinematics.  All arithmetic in the solver's scalar type T, per state.
  * Inputs, device pointers, component-major:
- *   q       [nq][N]   the sensor state: rows 3-6 the attitude, rows 7.. the joint angles.  Rows 0-2 are NEVER read.
+ *   q       [nq][N]   the sensor state: rows 3-6 the attitude (any non-zero quaternion: the law normalises it before it forms R), rows 7.. the joint
+ *                     angles.  Rows 0-2 are NEVER read.
  *   v       [nv][N]   rows 3-5 the world angular velocity, rows 6.. the joint rates.  Rows 0-2 are NEVER read.
  *   contact [N] int   bits 0-3: foot k senses ground (the estimated word of wbc_contact_estimate_batch, or the plant's)
  *   mask    [N] int   bits 0-3: the previous tick's stance mask

@@ -108,19 +108,23 @@ def _target_fn(P, kind, u):
     return {0: -3.0 + (0.7 * lo + 3.0) * u, 1: lo + (hi - lo) * (0.2 + 0.6 * u), 2: hi * (1.5 + 3.0 * u)}[kind % 3]
 
 
-def branch_case(flat, n, rank=0, P=None):
+def branch_case(flat, n, rank=0, P=None, states=None):
     """synth.make_batch(4, ...) states (tilted normals) with the joints moved to the STANDING posture of swing_ref.loop_ref_params (make_batch's own
     nominal posture folds the right legs next to a singular configuration: |det J_leg| down to 2e-6, below any useful det_min); Jc from the oracle;
     foot k of state i is of kind (i + 2 k) mod 8.  Per foot a force with a
     chosen normal component and a random tangential part is picked, f_prev is a random planned force, and the leg's joint rows of r are
-    J_leg^T (f - f_prev); the base rows of r are random (the law does not read them).  dict(Jc, r, f_prev, normals, contact, kinds [n, 4])"""
+    J_leg^T (f - f_prev); the base rows of r are random (the law does not read them).  dict(Jc, r, f_prev, normals, contact, kinds [n, 4])
+    states: dict(q, v, normals (unit)) taken as it is instead of the drawn batch (tests/walk_edges.py) -- no standing posture, and NO block is
+    doctored: a foot of kind 6 is then built like kind (i // 8) mod 6, and the singular legs are the ones the states bring along"""
     P = P or params()
     orc = GND._oracle(flat)
     legs = limit_ref.leg_joints(flat)
-    B = synth.make_batch(4, n, float(np.sum(flat["mass"])), rank=130 + rank)
+    B = synth.make_batch(4, n, float(np.sum(flat["mass"])), rank=130 + rank) if states is None else states
     rng = np.random.default_rng(synth.SEED + 1500 + rank)
     q = B["q"].copy()
-    q[:, 7:] += SR.loop_ref_params()["q_nom"] - np.tile(np.array(synth.NOMINAL_LEG), 4)
+    assert q.shape[0] == n
+    if states is None:
+        q[:, 7:] += SR.loop_ref_params()["q_nom"] - np.tile(np.array(synth.NOMINAL_LEG), 4)
     Jc = orc.dynamics(q, B["v"])["Jc"].copy()
     normals = B["normals"].copy()
     kinds = (np.arange(n)[:, None] + 2 * np.arange(4)[None, :]) % NKINDS
@@ -136,6 +140,8 @@ def branch_case(flat, n, rank=0, P=None):
         tang /= np.linalg.norm(tang, axis=1, keepdims=True)
         for i in range(n):
             kind = kinds[i, k]
+            if kind == 6 and states is not None:
+                kind = kinds[i, k] = (i // 8) % 6
             was = {0: 0, 1: 0, 2: 0, 3: 1, 4: 1, 5: 1, 6: i % 2, 7: (i // 2) % 2}[kind]
             contact[i] |= was << k
             fp = rng.uniform(0.0, 40.0) * nk[i] + rng.uniform(-8.0, 8.0) * tang[i]

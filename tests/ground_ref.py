@@ -132,17 +132,19 @@ def _kind(P, kind):
             4: (-0.6 * ft / kn, 0.0, 0.4), 5: (-1.4 * ft / kn, 0.0, 2.5)}[kind]
 
 
-def branch_case(flat, total_mass, n, rank=0, P=None):
-    """synth.make_batch(4, ...) states (tilted normals, three friction coefficients); per foot the leg's joint velocities are solved for so that the foot
+def branch_case(flat, total_mass, n, rank=0, P=None, states=None):
+    """synth.make_batch(4, ...) states (tilted normals, three friction coefficients; states: a batch of make_batch's keys with unit normals, taken
+    instead of drawing one -- tests/walk_edges.py); per foot the leg's joint velocities are solved for so that the foot
     has a chosen velocity, and `height` is placed so that it has a chosen gap: foot k of state i is of kind (i + 2 k) mod 6, and every 15th state
     (i mod 15 == 14) is a robot at rest but for pdot_z = -0.1 with n = e_z under every foot 5 mm in the ground -- v_f has one component, along n, so
     v_t = 0 exactly.  dict(q, v, normals, height, mu, dyn (M, h, Jc of the oracle), tau, tau_ext, kinds [n, 4] (-1 = the rest states))"""
     P = P or params()
     orc = _oracle(flat)
     legs = limit_ref.leg_joints(flat)
-    B = synth.make_batch(4, n, total_mass, rank=110 + rank)
+    B = synth.make_batch(4, n, total_mass, rank=110 + rank) if states is None else states
     rng = np.random.default_rng(synth.SEED + 1300 + rank)
     q, v, normals, mu = B["q"], B["v"].copy(), B["normals"].copy(), B["mu"]
+    assert q.shape[0] == n
     rest = np.arange(n) % REST_EVERY == REST_EVERY - 1
     v[rest] = 0.0
     v[rest, 2] = -0.1

@@ -123,14 +123,18 @@ JUNK_BITS = 0x50        # bits outside 0-3 of contact, mask and odo: not read
 BRANCH_DT = 2.0 ** -10
 
 
-def branch_case(flat, total_mass, n, rank=0, planes=True, stand=True):
+def branch_case(flat, total_mass, n, rank=0, planes=True, stand=True, states=None):
     """dict(q, v, contact, mask, normals, height (None without planes), base, anchor, odo, dt).  NaN in rows 0-2 of q and v and in the anchors of
     feet without an anchor bit; the anchors of the other feet lie within 2 cm of where the foot is.  stand: the synthetic model's standing posture
-    (joints in leg-major order); False leaves synth.make_batch's joints, for other models."""
-    B = synth.make_batch(4, n, total_mass, rank=170 + rank)
+    (joints in leg-major order); False leaves synth.make_batch's joints, for other models.
+    states: dict(q, v, normals (unit)) taken as it is instead of the drawn batch (tests/walk_edges.py): p_true is then the states' own base
+    position, and every plane passes within 2 cm of its foot (height from the foot's own position: a plane through the origin would put a base
+    50 m out 50 m from its ground)."""
+    B = synth.make_batch(4, n, total_mass, rank=170 + rank) if states is None else states
     rng = np.random.default_rng(synth.SEED + 1700 + rank)
     q, v = B["q"].copy(), B["v"].copy()
-    if stand:
+    assert q.shape[0] == n
+    if stand and states is None:
         q[:, 7:] += SR.loop_ref_params()["q_nom"] - np.tile(np.array(synth.NOMINAL_LEG), 4)
     i = np.arange(n)
     S = (i % 16).astype(np.int32)
@@ -140,6 +144,8 @@ def branch_case(flat, total_mass, n, rank=0, planes=True, stand=True):
     contact = S | np.where(why == 1, free, 0)
     mask = S | np.where(why == 0, free, 0)
     p_true = np.stack([rng.uniform(-1.0, 1.0, n), rng.uniform(-1.0, 1.0, n), rng.uniform(0.35, 0.45, n)], 1)
+    if states is not None:
+        p_true = q[:, 0:3].copy()
     lever, _ = leg_terms(flat, q, v)
     anchor = (p_true[:, None, :] + lever + rng.uniform(-0.02, 0.02, (n, 4, 3)))
     anchor[~_bits(odo)] = np.nan
@@ -148,6 +154,8 @@ def branch_case(flat, total_mass, n, rank=0, planes=True, stand=True):
     v[:, 0:3] = np.nan
     normals = B["normals"].copy() if planes else None
     height = rng.uniform(-0.02, 0.02, (n, 4)) if planes else None
+    if planes and states is not None:
+        height = height + (normals.reshape(n, 4, 3) * (p_true[:, None, :] + lever)).sum(2)
     return dict(q=q, v=v, contact=(contact | JUNK_BITS).astype(np.int32), mask=(mask | JUNK_BITS).astype(np.int32), normals=normals, height=height,
                 base=base, anchor=anchor.reshape(n, 12), odo=(odo | JUNK_BITS).astype(np.int32), dt=BRANCH_DT)
 

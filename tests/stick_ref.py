@@ -94,11 +94,11 @@ REST_RATIO = (0.5, 2.0)
 JUNK = 7.25
 
 
-def branch_case(flat, total_mass, n, rank=0, P=None, k_t=DEFAULT_KT):
-    """ground_ref.branch_case + anchor [n, 12], stick [n] int32"""
+def branch_case(flat, total_mass, n, rank=0, P=None, k_t=DEFAULT_KT, states=None):
+    """ground_ref.branch_case (states: handed through) + anchor [n, 12], stick [n] int32"""
     P = P or R.params()
     legs = limit_ref.leg_joints(flat)
-    c = R.branch_case(flat, total_mass, n, rank=rank, P=P)
+    c = R.branch_case(flat, total_mass, n, rank=rank, P=P, states=states)
     g = R.ground_force(P, c["q"], c["v"], c["dyn"]["Jc"], c["normals"], c["height"], c["mu"], legs)
     rng = np.random.default_rng(synth.SEED + 1400 + rank)
     rest = c["kinds"][:, 0] == -1

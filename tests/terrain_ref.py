@@ -157,33 +157,34 @@ def branch_case(T, m, rank=0):
 FEET_SIZES = GR.PARITY_SIZES
 
 
-def fit_grid(flat, q, mask=None, swing=None, tile=None):
-    """The rippled 64 x 48 x 4 grid (cell 2^-6) moved under a batch: its origin is the batch's mean foot position minus half the grid, rounded to 1/16
-    of a cell, then shifted by the first of j / 16 cells, j = 0 .. 15 (x and y alike), at which every sample feet() takes keeps MARGIN64 / MARGIN32
-    clear of a cell edge in float64 / float32.  -> (T, feet() in float64, feet() in float32)"""
+def fit_grid(flat, q, mask=None, swing=None, tile=None, nx=64, ny=48):
+    """The rippled 64 x 48 x 4 grid (cell 2^-6; nx, ny: another size) moved under a batch: its origin is the batch's mean foot position minus half the
+    grid, rounded to 1/16 of a cell, then shifted by the first of j / 16 cells, j = 0 .. 15 (x and y alike), at which every sample feet() takes keeps
+    MARGIN64 / MARGIN32 clear of a cell edge in float64 / float32.  -> (T, feet() in float64, feet() in float32)"""
     n = q.shape[0]
     pf = np.stack([SR.foot_kin(flat, k, q, np.zeros((n, q.shape[1] - 1)))["pf"] for k in range(4)], 1)
     cell = 2.0 ** -6
-    ox, oy = (np.round((pf[:, :, i].mean() - 0.5 * (m - 1) * cell) / cell * 16) / 16 * cell for i, m in ((0, 64), (1, 48)))
+    ox, oy = (np.round((pf[:, :, i].mean() - 0.5 * (m - 1) * cell) / cell * 16) / 16 * cell for i, m in ((0, nx), (1, ny)))
     f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
     for j in range(16):
-        T = grid_ripple(64, 48, ox + j * cell / 16, oy + j * cell / 16, cell, 0.1, 0.05, 0.006, 0.125, 0.25, 4)
+        T = grid_ripple(nx, ny, ox + j * cell / 16, oy + j * cell / 16, cell, 0.1, 0.05, 0.006, 0.125, 0.25, 4)
         F64, F32 = feet(flat, T, q, mask, swing, tile), feet(flat, T, f32(q), mask, f32(swing), tile)
         if F64["margin"] >= MARGIN64 and F32["margin"] >= MARGIN32:
             return T, F64, F32
     raise AssertionError("no grid offset keeps the case clear of the cell edges")
 
 
-def feet_case(flat, total_mass, n, rank=0):
-    """gait_ref.branch_case states with every mask pattern (swing_ref.all_masks), plans whose p1_x, p1_y lie within 5 cm of the foot (the other
-    swing words stay recognisable junk), tile i mod 4, and fit_grid's terrain.  dict(q, mask, swing, tile, T, ref64, ref32)"""
+def feet_case(flat, total_mass, n, rank=0, q=None, nx=64, ny=48):
+    """gait_ref.branch_case states (q: these instead -- tests/walk_edges.py) with every mask pattern (swing_ref.all_masks), plans whose p1_x, p1_y lie
+    within 5 cm of the foot (the other swing words stay recognisable junk), tile i mod 4, and fit_grid's terrain (of nx x ny nodes).
+    dict(q, mask, swing, tile, T, ref64, ref32)"""
     c = GR.branch_case(flat, total_mass, n, rank=rank)
     rng = np.random.default_rng(synth.SEED + 1520 + rank)
-    q, swing = c["q"], c["swing"].copy()
+    q, swing = c["q"] if q is None else q, c["swing"].copy()
     for k in range(4):
         swing[:, 9 * k + 3:9 * k + 5] = SR.foot_kin(flat, k, q, np.zeros((n, 18)))["pf"][:, :2] + rng.uniform(-0.05, 0.05, (n, 2))
     mask, tile = SR.all_masks(n), (np.arange(n) % 4).astype(np.int32)
-    T, F64, F32 = fit_grid(flat, q, mask, swing, tile)
+    T, F64, F32 = fit_grid(flat, q, mask, swing, tile, nx, ny)
     return dict(q=q, mask=mask, swing=swing, tile=tile, T=T, ref64=F64, ref32=F32)
 
 
