@@ -297,6 +297,21 @@ class QuadrupedWBC {
           "wbc_gait_estimated_odom_batch");
   }
 
+  // Trunk reference from the velocity command (wbc_hip.h, "Trunk reference from the velocity command"): w_des and vdot_des from cmd and the foot
+  // planes instead of a host-written plan.  trunk [6][N] is a caller-owned DEVICE buffer, advanced in place; reset [N] non-zero (first call) starts it
+  // from the state.  referenceCmdSwing is referenceCmd, then the swing law at t = 0, one launch.  (The argument order of the C calls.)
+  void setTrunkParams(const wbc_trunk_params& p) { check(wbc_solver_set_trunk_params(solver_, &p), "wbc_solver_set_trunk_params"); }
+  void referenceCmd(size_t N, const void* q, const void* v, const void* cmd, const void* normals, const void* height, const int* reset /* may be nullptr */,
+                    void* trunk, void* w_des, void* vdot_des, void* com = nullptr, void* ref = nullptr, void* stream = nullptr) {
+    check(wbc_reference_cmd_batch(solver_, N, q, v, cmd, normals, height, reset, trunk, w_des, vdot_des, com, ref, stream), "wbc_reference_cmd_batch");
+  }
+  void referenceCmdSwing(size_t N, const void* q, const void* v, const void* cmd, const void* normals, const void* height,
+                         const int* reset /* may be nullptr */, void* trunk, const int* mask, const void* swing, void* w_des, void* vdot_des,
+                         void* com = nullptr, void* ref = nullptr, void* foot = nullptr, void* stream = nullptr) {
+    check(wbc_reference_cmd_swing_batch(solver_, N, q, v, cmd, normals, height, reset, trunk, mask, swing, w_des, vdot_des, com, ref, foot, stream),
+          "wbc_reference_cmd_swing_batch");
+  }
+
   // Joint torque limits (wbc_hip.h, "Joint torque limits behind a tick").  effortLimits(): the URDF's <limit effort> per joint in jointNames() order,
   // HUGE_VAL where it gives none.  setTorqueLimits(): the limits the post-pass enforces (one value > 0 per joint; empty = back to the URDF's).
   std::vector<double> effortLimits() const {

@@ -965,6 +965,93 @@ int wbc_gait_estimated_odom_batch(wbc_solver* s, size_t N, const void* q, const 
 int wbc_compute_base_estimate(wbc_solver* s, const double* q, const double* v, int contact, int mask, const double* normals /* may be NULL with height */,
                               const double* height, double* base, double* anchor, int* odo, double* q_est, double* v_est);
 
+/* Trunk reference from the velocity command: turning, leash, terrain posture.  ADDITIVE to ABI 10 (wbc_abi_version() stays 10, no existing struct,
+ * default or kernel changes; the feature is detected by these symbols).  wbc_reference[_swing]_batch track plan [12][N], a quintic between two points
+ * with one fixed quat_des that the host writes.  These calls form the trunk's reference on the device from the cmd buffer the gait call reads
+ * (rows 0-2: vx, vy in the heading frame, wz; row 3 is not read) and from the normals / height planes the terrain call writes (on flat ground:
+ * (0, 0, 1) and the ground's height), and advance a small per-robot state in place.  The walking tick becomes
+ *     gait[_estimated][_terrain[_select]] -> reference_cmd_swing -> step -> integrate_ground[_stick]
+ * still four launches; with q_est, v_est of the odometry call it reads no base row of the plant.
+ *   trunk [WBC_TRUNK_WORDS][N], solver scalar type, component-major, caller-owned, advanced IN PLACE:
+ *     0,1 x, y of the reference CoM   2 psi, reference heading in (-pi, pi]   3 z_s, support height at (x, y)   4,5 s_x, s_y, support slopes dz/dx, dz/dy
+ *   To start a robot pass reset [N] non-zero for it in its first call (trunk's words are then not read, except z_s where no foot plane qualifies), or
+ *   store x, y = the CoM, psi = the heading, z_s = the ground's height under it and zero slopes.
+ *   ref [WBC_TRUNKREF_WORDS][N], optional output: c_ref (3), cd_ref (3), quat_des (x, y, z, w).
+ * The law, per state, in the solver's scalar type T, in this order.  dt is the solver's control period; dt, pi, 2 pi and cos(yaw_leash) are formed on
+ * the host in double and rounded to T.  c, cd: the CoM position and velocity of (q, v) as wbc_reference_batch forms them.  p_f,k: foot k's world
+ * position from the leg's position chain (origins down the leg in base coordinates, as the gait call latches p0).  h_r = (R00, R10) normalised: the
+ * trunk's heading, as in the gait call.
+ *   0 reset (where reset is given and non-zero): (x, y) := c_xy; psi := atan2(h_r,y, h_r,x); step 3 runs with a_s = 1 -- as assignments, z_s := z*,
+ *     s_x := b, s_y := c, so that no word of trunk is read (it may hold anything, NaN included) -- and the slopes become 0 if there is no fit (also
+ *     with no qualifying foot at all; z_s is then kept as given: the one word a reset can read).
+ *   1 heading: psi+ = psi + wz dt; g(a) = h_r . (cos a, sin a); the heading advances iff g(psi+) >= cos(yaw_leash) or g(psi+) >= g(psi), and then
+ *     w_des_z = wz; otherwise psi+ = psi and w_des_z = 0.  Then the wrap: psi+ > pi subtracts 2 pi, psi+ <= -pi adds 2 pi.
+ *   2 position: v_w = Rz(psi+)(vx, vy); (x+, y+) = (x, y) + v_w dt; e = (x+, y+) - c_xy; |e|^2 > leash^2: (x+, y+) = c_xy + e leash rsqrt(|e|^2).
+ *   3 support plane under the four feet (lifted ones too: the terrain call writes a plane under each): w_k = (n_k,z >= nz_min);
+ *     zs_k = (d_k - n_k,x p_f,x - n_k,y p_f,y) / n_k,z, the surface height under the foot; m = sum w_k.
+ *     m >= 1: means xb, yb, zb over those feet, centred sums Sxx, Sxy, Syy, Sxz, Syz, det = Sxx Syy - Sxy^2.
+ *     m >= 3 and det > det_min: b = (Syy Sxz - Sxy Syz) / det, c = (Sxx Syz - Sxy Sxz) / det; s_x += a_s (b - s_x), s_y += a_s (c - s_y);
+ *       z* = zb + b (x+ - xb) + c (y+ - yb).
+ *     m >= 1 otherwise (two feet, collinear feet): the slopes are held; z* = zb + s_x (x+ - xb) + s_y (y+ - yb).
+ *     m = 0: z_s, s_x, s_y are held.                                 In the first three cases z_s += a_s (z* - z_s).
+ *   4 reference: c_ref = (x+, y+, z_s + height); cd_ref = (v_w, s_x v_w,x + s_y v_w,y); cdd_ref = 0.
+ *   5 desired attitude: n = (-tilt s_x, -tilt s_y, 1) normalised; q_tilt = (-n_y, n_x, 0, 1 + n_z) normalised, the shortest rotation that takes e_z
+ *     to n (no branch: n_z > 0); q_yaw = (0, 0, sin psi+/2, cos psi+/2); quat_des = q_tilt (x) q_yaw.  quat_des takes e_z to n exactly.  The trunk's
+ *     x axis then has heading psi+ exactly where the slope lies along or across the heading, and within (1 - cos theta) / (2 cos theta) ~ theta^2 / 4
+ *     rad of it otherwise (theta = the lean angle: 0.01 rad on a 0.2 slope).
+ *   6 outputs: a_cmd = kp_com o (c_ref - c) + kd_com o (cd_ref - cd); alpha_cmd = kp_rot o e_R + kd_rot o ((0, 0, w_des_z) - omega), e_R and omega
+ *     as wbc_reference_batch forms and reads them; the joint posture rows, F and w_des as there, with the solver's wbc_ref_params
+ *     (wbc_solver_set_ref_params must have been called).  In the fused call the swing law follows as in wbc_reference_swing_batch, at t = 0 (the gait
+ *     call wrote t0).
+ *   7 trunk is stored, and ref if given.
+ * Exact words: psi and w_des_z where the heading is held; z_s, s_x, s_y bit for bit where m = 0, and s_x, s_y bit for bit where there is no fit
+ * (in a reset: exactly 0).  The device forms every product of steps 0-6 (p_f included) unfused, in both kernels; it differs
+ * from another evaluation of the law only by its sin / cos / atan2 / rsqrt and by the fused products inside c and cd: every other word holds to
+ * rounding.
+ * wbc_reference_cmd_swing_batch is ONE launch in both scalar types.  Its trunk, ref, w_des, com, base rows and stance-leg rows are bit-identical to
+ * wbc_reference_cmd_batch's; the swing rows equal wbc_reference_cmd_batch followed by wbc_swing_reference_batch (t = 0) to rounding.
+ * How the defaults were fixed: on the CPU, in the two loops of tests/trunk_ref.py (gait -> terrain planes -> this law -> swing law -> tick -> the
+ * stiction plant, dt 2^-10; tests/test_trunk_oracle.py holds the figures).  Loop A, 4 robots on flat ground, vx 0.1, wz 0.5, 1 024 ticks: the trunk
+ * yaws 0.494 rad of 0.5 commanded (the plan-driven loop: 0.007, and its CoM stops after 0.049 m where this one walks 0.097 of 0.1); |c_ref - c| <= 5.9
+ * mm; the CoM 1.8 .. 4.6 mm above `height` over the support.  Loop B, 2 robots, vx 0.15, 6 144 ticks, flat ground into a 0.2 ramp: the fitted slope
+ * goes 0 -> 0.200, pitch settles at -0.172 rad, the CoM stays 0.5 .. 8.1 mm above `height` over the fitted support, |c_ref - c| <= 12.3 mm, the CoM
+ * travels 0.888 m of 0.9 and climbs 0.115 m.  Every QP status 0 in both.  Tried: a_s 2^-3 and 2^-7 (loop B within 0.5 mm / 0.0004 rad of 2^-5:
+ * kept); tilt 0 and 0.5 (pitch -0.007 / -0.090, every status 0: 1 kept, the trunk parallel to its support); leash 0.004 (acts: 2 mm less path in
+ * loop A; 0.05 never acts in either loop and is a guard against a stuck robot, not a tracking term); yaw_leash 0.01 and 0.002 (hold the heading in
+ * 784 and 2 584 of 4 096 robot-ticks, yaw 0.398 / 0.183 rad; 0.5 never holds).  The issue's starting values stood.
+ * wbc_trunk_params: height non-finite; leash <= 0 or NaN (+inf is allowed: no leash); yaw_leash outside (0, pi]; a_s or tilt outside [0, 1]; nz_min
+ * outside (0, 1]; det_min <= 0 or non-finite; a struct_size too small: WBC_E_INVALID.  The bounds hold in the solver's scalar type: on an fp32 solver a
+ * leash, nz_min or det_min that rounds to 0, or a det_min or height that overflows, is refused as well.  The values travel as a kernel argument: nothing is uploaded,
+ * later calls use them.  Not inside a stream capture (a captured graph keeps the values it was captured with).
+ * Stream rules as for wbc_reference_swing_batch: no allocation, no synchronisation, hipGraph-capturable; N == 0 returns WBC_OK without looking at
+ * anything; a NULL required pointer: WBC_E_INVALID; N > max_batch: WBC_E_CAPACITY -- all before the device is touched.
+ * wbc_compute_reference_cmd: the single-robot host-pointer form (fp64 solvers; synchronises); trunk[6] in/out.
+ * Out of scope: the rollout kernels and wbc_rollout_*; wbc_multi_*; a pitch/roll-rate feed-forward; a convex-MPC force plan; CoM references shaped by
+ * the gait phase. */
+#define WBC_TRUNK_WORDS 6
+#define WBC_TRUNKREF_WORDS 10
+typedef struct wbc_trunk_params {
+  size_t struct_size;   /* sizeof(wbc_trunk_params) of the caller's build */
+  double height;        /* CoM height above the support, m, finite */
+  double leash;         /* m, > 0 (may be +inf): the reference CoM stays within this distance of the CoM */
+  double yaw_leash;     /* rad, 0 < yaw_leash <= pi: the reference heading is not advanced further away from the trunk's than this */
+  double a_s;           /* 0 <= a_s <= 1: per-tick blend of the support plane */
+  double tilt;          /* 0 <= tilt <= 1: share of the support slope the trunk leans with */
+  double nz_min;        /* 0 < nz_min <= 1: a foot plane flatter than this in n_z is left out of the support */
+  double det_min;       /* m^4, > 0: smallest determinant of the fit */
+} wbc_trunk_params;
+void wbc_trunk_params_default(wbc_trunk_params* p);
+int wbc_solver_set_trunk_params(wbc_solver* s, const wbc_trunk_params* p);
+int wbc_reference_cmd_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* normals, const void* height,
+                            const int* reset /* may be NULL, [N] */, void* trunk /* in/out [6][N] */, void* w_des, void* vdot_des,
+                            void* com /* may be NULL */, void* ref /* may be NULL, [10][N] */, void* stream);
+int wbc_reference_cmd_swing_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* normals, const void* height,
+                                  const int* reset /* may be NULL, [N] */, void* trunk /* in/out [6][N] */, const int* mask, const void* swing,
+                                  void* w_des, void* vdot_des, void* com /* may be NULL */, void* ref /* may be NULL */, void* foot /* may be NULL */,
+                                  void* stream);
+int wbc_compute_reference_cmd(wbc_solver* s, const double* q, const double* v, const double* cmd, const double* normals, const double* height,
+                              int reset, double* trunk, double* w_des, double* vdot_des, double* com /* may be NULL */, double* ref /* may be NULL */);
+
 /* Single-robot, host-pointer, double-precision convenience call: the shape of the reference's
  * one-robot tick (BASELINE.json configs[0]).  Runs wbc_step_batch with N = 1 on the GPU and
  * synchronises.  obs_integ/obs_r (host, nv each) are in/out and may be NULL when the observer is off. */

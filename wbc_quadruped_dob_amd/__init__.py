@@ -309,6 +309,14 @@ def lib():
             L.wbc_base_estimate_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 12
             L.wbc_gait_estimated_odom_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 20
             L.wbc_compute_base_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
+        # trunk reference from the velocity command: additive to ABI 10, detected by the symbols in the same way (_trunk_lib)
+        if hasattr(L, "wbc_reference_cmd_swing_batch"):
+            L.wbc_trunk_params_default.argtypes = [C.c_void_p]
+            L.wbc_trunk_params_default.restype = None
+            L.wbc_solver_set_trunk_params.argtypes = [C.c_void_p, C.c_void_p]
+            L.wbc_reference_cmd_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 12
+            L.wbc_reference_cmd_swing_batch.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 15
+            L.wbc_compute_reference_cmd.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
         L.wbc_plan_tick.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_solver_plan_tick.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.wbc_step_batch_warm.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
@@ -549,6 +557,44 @@ class ContactParams(C.Structure):
 
     def as_dict(self):
         return dict(f_on=self.f_on, f_off=self.f_off, det_min=self.det_min)
+
+
+def _trunk_lib():
+    """lib(), for the trunk-reference calls: a library without their symbols is an older build of the same ABI"""
+    L = lib()
+    if not hasattr(L, "wbc_reference_cmd_swing_batch"):
+        raise RuntimeError("%s lacks the trunk-reference entry points: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
+    return L
+
+
+TRUNK_WORDS = 6       # include/wbc_hip.h: WBC_TRUNK_WORDS -- trunk [TRUNK_WORDS, N]: x, y, psi, z_s, s_x, s_y
+TRUNKREF_WORDS = 10   # include/wbc_hip.h: WBC_TRUNKREF_WORDS -- ref [TRUNKREF_WORDS, N]: c_ref (3), cd_ref (3), quat_des (x, y, z, w)
+
+
+class TrunkParams(C.Structure):
+    """wbc_trunk_params: the trunk reference from the velocity command (include/wbc_hip.h, "Trunk reference from the velocity command")"""
+    _fields_ = [("struct_size", C.c_size_t), ("height", C.c_double), ("leash", C.c_double), ("yaw_leash", C.c_double), ("a_s", C.c_double),
+                ("tilt", C.c_double), ("nz_min", C.c_double), ("det_min", C.c_double)]
+    FIELDS = ("height", "leash", "yaw_leash", "a_s", "tilt", "nz_min", "det_min")
+
+    @staticmethod
+    def default():
+        p = TrunkParams()
+        _trunk_lib().wbc_trunk_params_default(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_dict(d):
+        """keys height, leash, yaw_leash, a_s, tilt, nz_min, det_min; missing keys keep the defaults"""
+        p = TrunkParams.default()
+        for k, val in d.items():
+            if k not in TrunkParams.FIELDS:
+                raise KeyError("TrunkParams has no field %r" % k)
+            setattr(p, k, float(val))
+        return p
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in TrunkParams.FIELDS}
 
 
 class OdomParams(C.Structure):
@@ -1142,6 +1188,68 @@ class Solver:
                                                       self._ptr(out["foot"], FOOT_WORDS, N) if want_foot else None, self._stream()),
                "wbc_reference_swing_batch")
         return out
+
+    def set_trunk_params(self, p):
+        """p: TrunkParams or dict (see TrunkParams.from_dict): the parameters of every later reference_cmd call of this solver."""
+        if isinstance(p, dict):
+            p = TrunkParams.from_dict(p)
+        _check(_trunk_lib().wbc_solver_set_trunk_params(self._h, C.byref(p)), "wbc_solver_set_trunk_params")
+
+    def _cmd_out(self, N, out, want_com, want_ref, want_foot):
+        m = self.model
+        out = {} if out is None else out
+        for k, rows in ((("w_des", 6), ("vdot_des", m.nv)) + ((("com", 6),) if want_com else ()) + ((("ref", TRUNKREF_WORDS),) if want_ref else ())
+                        + ((("foot", FOOT_WORDS),) if want_foot else ())):
+            if k not in out:
+                out[k] = self.empty(rows, N)
+        return out
+
+    def reference_cmd(self, q, v, cmd, normals, height, trunk, reset=None, out=None, want_com=False, want_ref=False):
+        """Trunk reference from the velocity command (wbc_reference_cmd_batch): cmd [4, N] (rows 0-2 are read), normals [12, N] and height [4, N] the
+        plane under every foot, trunk [TRUNK_WORDS, N] advanced IN PLACE, reset (int32 [N] or None): non-zero starts a robot's trunk words from its
+        state.  Returns dict(w_des [6, N], vdot_des [nv, N], trunk[, com [6, N]][, ref [TRUNKREF_WORDS, N]])."""
+        m = self.model
+        N = q.shape[1]
+        out = self._cmd_out(N, out, want_com, want_ref, False)
+        _check(_trunk_lib().wbc_reference_cmd_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(cmd, GAIT_CMD_WORDS, N),
+                                                    self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N),
+                                                    self._ptr(reset, 1, N, self.torch.int32), self._ptr(trunk, TRUNK_WORDS, N),
+                                                    self._ptr(out["w_des"], 6, N), self._ptr(out["vdot_des"], m.nv, N),
+                                                    self._ptr(out["com"], 6, N) if want_com else None,
+                                                    self._ptr(out["ref"], TRUNKREF_WORDS, N) if want_ref else None, self._stream()),
+               "wbc_reference_cmd_batch")
+        out["trunk"] = trunk
+        return out
+
+    def reference_cmd_swing(self, q, v, cmd, normals, height, trunk, mask, swing, reset=None, out=None, want_com=False, want_ref=False,
+                            want_foot=False):
+        """reference_cmd() followed by swing_reference() at t = 0, as one launch (wbc_reference_cmd_swing_batch):
+        dict(w_des, vdot_des, trunk[, com][, ref][, foot [FOOT_WORDS, N]])."""
+        m = self.model
+        N = q.shape[1]
+        i32 = self.torch.int32
+        out = self._cmd_out(N, out, want_com, want_ref, want_foot)
+        _check(_trunk_lib().wbc_reference_cmd_swing_batch(self._h, N, self._ptr(q, m.nq, N), self._ptr(v, m.nv, N), self._ptr(cmd, GAIT_CMD_WORDS, N),
+                                                          self._ptr(normals, 3 * m.nf, N), self._ptr(height, m.nf, N), self._ptr(reset, 1, N, i32),
+                                                          self._ptr(trunk, TRUNK_WORDS, N), self._ptr(mask, 1, N, i32),
+                                                          self._ptr(swing, SWING_WORDS, N), self._ptr(out["w_des"], 6, N),
+                                                          self._ptr(out["vdot_des"], m.nv, N), self._ptr(out["com"], 6, N) if want_com else None,
+                                                          self._ptr(out["ref"], TRUNKREF_WORDS, N) if want_ref else None,
+                                                          self._ptr(out["foot"], FOOT_WORDS, N) if want_foot else None, self._stream()),
+               "wbc_reference_cmd_swing_batch")
+        out["trunk"] = trunk
+        return out
+
+    def compute_reference_cmd(self, q, v, cmd, normals, height, trunk, reset=0):
+        """Single-robot host-array form of reference_cmd (numpy float64, fp64 solvers): returns (trunk[6], w_des[6], vdot_des[18], com[6], ref[10]);
+        the inputs are not modified."""
+        arr = lambda a, n: np.ascontiguousarray(np.asarray(a, np.float64).reshape(n))
+        q, v, cmd, normals, height, trunk = arr(q, 19), arr(v, 18), arr(cmd, 4), arr(normals, 12), arr(height, 4), arr(trunk, 6).copy()
+        w, vd, com, ref = np.empty(6), np.empty(18), np.empty(6), np.empty(TRUNKREF_WORDS)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(_trunk_lib().wbc_compute_reference_cmd(self._h, p(q), p(v), p(cmd), p(normals), p(height), int(reset), p(trunk), p(w), p(vd), p(com),
+                                                      p(ref)), "wbc_compute_reference_cmd")
+        return trunk, w, vd, com, ref
 
     def compute_swing_reference(self, q, v, mask, swing, vdot_des, t=0.0):
         """Single-robot host-array form of swing_reference (numpy float64, fp64 solvers): returns (vdot_des[nv] with the swing legs' rows replaced,

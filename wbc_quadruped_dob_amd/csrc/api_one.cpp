@@ -273,3 +273,25 @@ extern "C" int wbc_compute_base_estimate(wbc_solver* s, const double* q, const d
   *odo = hi[2];
   return WBC_OK;
 }
+
+extern "C" int wbc_compute_reference_cmd(wbc_solver* s, const double* q, const double* v, const double* cmd, const double* normals, const double* height,
+                                         int reset, double* trunk, double* w_des, double* vdot_des, double* com, double* ref) {
+  if (!s || !q || !v || !cmd || !normals || !height || !trunk || !w_des || !vdot_des) return fail(WBC_E_INVALID, "null argument");
+  if (s->dtype != WBC_F64) return fail(WBC_E_INVALID, "wbc_compute_reference_cmd: fp64 solvers only");
+  ON_DEVICE(s);
+  const int oq = 0, ov = 19, oc = 37, on = 41, oh = 53, ot = 57, ow = 63, oa = 69, om = 87, orf = 93;   // q v cmd normals height | trunk w_des vdot_des com ref, one int: reset
+  double h[orf + TRUNKREF_WORDS];
+  static_assert(orf + TRUNKREF_WORDS <= STAGE_ONE_DOUBLES, "the staging block holds this call");
+  std::memset(h, 0, sizeof(h));
+  std::memcpy(h + oq, q, 19 * sizeof(double)); std::memcpy(h + ov, v, 18 * sizeof(double)); std::memcpy(h + oc, cmd, 4 * sizeof(double));
+  std::memcpy(h + on, normals, 12 * sizeof(double)); std::memcpy(h + oh, height, 4 * sizeof(double)); std::memcpy(h + ot, trunk, 6 * sizeof(double));
+  int hi[1] = {reset};
+  const int rc = stage_one(s, h, ow, hi, 1, ot, orf + TRUNKREF_WORDS - ot, 0, [&](double* d, int* di) {
+    return wbc_reference_cmd_batch(s, 1, d + oq, d + ov, d + oc, d + on, d + oh, di, d + ot, d + ow, d + oa, d + om, d + orf, nullptr);
+  });
+  if (rc) return rc;
+  std::memcpy(trunk, h + ot, 6 * sizeof(double)); std::memcpy(w_des, h + ow, 6 * sizeof(double)); std::memcpy(vdot_des, h + oa, 18 * sizeof(double));
+  if (com) std::memcpy(com, h + om, 6 * sizeof(double));
+  if (ref) std::memcpy(ref, h + orf, TRUNKREF_WORDS * sizeof(double));
+  return WBC_OK;
+}

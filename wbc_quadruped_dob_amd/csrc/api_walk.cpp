@@ -532,3 +532,80 @@ extern "C" int wbc_gait_estimated_odom_batch(wbc_solver* s, size_t N, const void
     return k_gait_estimated_odom<T>(L, dev_model<T>(s), a);
   });
 }
+
+// ---- trunk reference from the velocity command: the parameters, the argument builder, the reference call and the call with the swing law fused in
+extern "C" void wbc_trunk_params_default(wbc_trunk_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->height = 0.4; p->leash = 0.05; p->yaw_leash = 0.5; p->a_s = 0.03125; p->tilt = 1.0; p->nz_min = 0.5; p->det_min = 1e-6;   // how they were fixed: include/wbc_hip.h
+}
+
+extern "C" int wbc_solver_set_trunk_params(wbc_solver* s, const wbc_trunk_params* p) {
+  if (!s || !p) return fail(WBC_E_INVALID, "null argument");
+  if (const int rc = check_struct_size(p, "wbc_trunk_params: struct_size too small (call wbc_trunk_params_default first)")) return rc;
+  if (!std::isfinite(p->height)) return fail(WBC_E_INVALID, "wbc_trunk_params: height must be finite");
+  if (!(p->leash > 0)) return fail(WBC_E_INVALID, "wbc_trunk_params: leash must be > 0 (+inf allowed)");
+  if (!(p->yaw_leash > 0 && p->yaw_leash <= 3.14159265358979323846)) return fail(WBC_E_INVALID, "wbc_trunk_params: 0 < yaw_leash <= pi");
+  if (!(p->a_s >= 0 && p->a_s <= 1)) return fail(WBC_E_INVALID, "wbc_trunk_params: 0 <= a_s <= 1");
+  if (!(p->tilt >= 0 && p->tilt <= 1)) return fail(WBC_E_INVALID, "wbc_trunk_params: 0 <= tilt <= 1");
+  if (!(p->nz_min > 0 && p->nz_min <= 1)) return fail(WBC_E_INVALID, "wbc_trunk_params: 0 < nz_min <= 1");
+  if (!(p->det_min > 0) || !std::isfinite(p->det_min)) return fail(WBC_E_INVALID, "wbc_trunk_params: det_min must be finite and > 0");
+  // the kernels hold the values in the solver's scalar type: the bounds must survive the rounding (an fp32 solver: nz_min = 1e-300 would become 0, a
+  // plane with n_z = 0 would pass, and its division would put NaN into trunk).  Behind the range checks: those never read the solver
+  if (s->dtype == WBC_F32) {
+    if (!((float)p->leash > 0)) return fail(WBC_E_INVALID, "wbc_trunk_params: leash rounds to 0 in the solver's scalar type");
+    if (!((float)p->nz_min > 0)) return fail(WBC_E_INVALID, "wbc_trunk_params: nz_min rounds to 0 in the solver's scalar type");
+    if (!((float)p->det_min > 0) || !std::isfinite((float)p->det_min))
+      return fail(WBC_E_INVALID, "wbc_trunk_params: det_min rounds to 0 or overflows in the solver's scalar type");
+    if (!std::isfinite((float)p->height)) return fail(WBC_E_INVALID, "wbc_trunk_params: height overflows in the solver's scalar type");
+  }
+  s->trunk = *p;
+  return WBC_OK;
+}
+
+template <class T>
+static void cmd_ref_args(CmdRefArgs<T>& a, const wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* normals,
+                         const void* height, const int* reset, void* trunk, void* w_des, void* vdot_des, void* com, void* ref) {
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.q = (const T*)q; a.v = (const T*)v; a.cmd = (const T*)cmd; a.normals = (const T*)normals; a.height = (const T*)height;
+  a.reset = reset; a.trunk = (T*)trunk; a.w_des = (T*)w_des; a.vdot_des = (T*)vdot_des; a.com = (T*)com; a.ref = (T*)ref;
+  a.jpack = s->jpack;
+  const wbc_trunk_params& t = s->trunk;
+  const double pi = 3.14159265358979323846;
+  a.P.height = (T)t.height; a.P.leash = (T)t.leash; a.P.a_s = (T)t.a_s; a.P.tilt = (T)t.tilt; a.P.nz_min = (T)t.nz_min; a.P.det_min = (T)t.det_min;
+  a.P.dt = (T)s->params.dt; a.P.pi = (T)pi; a.P.two_pi = (T)(2.0 * pi); a.P.cos_yl = (T)std::cos(t.yaw_leash);
+}
+
+extern "C" int wbc_reference_cmd_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* normals, const void* height,
+                                       const int* reset, void* trunk, void* w_des, void* vdot_des, void* com, void* ref, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !normals || !height || !trunk || !w_des || !vdot_des) return fail(WBC_E_INVALID, "null argument");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  if (!s->d_ref) return fail(WBC_E_INVALID, "call wbc_solver_set_ref_params first");
+  return launch_batch(s, N, stream, "reference cmd", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    CmdRefArgs<T> a;
+    cmd_ref_args(a, s, N, q, v, cmd, normals, height, reset, trunk, w_des, vdot_des, com, ref);
+    return k_reference_cmd<T>(L, dev_model<T>(s), (const DevRefParams<T>*)s->d_ref, a);
+  });
+}
+
+extern "C" int wbc_reference_cmd_swing_batch(wbc_solver* s, size_t N, const void* q, const void* v, const void* cmd, const void* normals,
+                                             const void* height, const int* reset, void* trunk, const int* mask, const void* swing, void* w_des,
+                                             void* vdot_des, void* com, void* ref, void* foot, void* stream) {
+  if (!s) return fail(WBC_E_INVALID, "null solver");
+  if (N == 0) return WBC_OK;
+  if (!q || !v || !cmd || !normals || !height || !trunk || !mask || !swing || !w_des || !vdot_des) return fail(WBC_E_INVALID, "null argument");
+  if (N > s->max_batch) return fail(WBC_E_CAPACITY, "N exceeds the solver's max_batch");
+  if (!s->d_ref) return fail(WBC_E_INVALID, "call wbc_solver_set_ref_params first");
+  return launch_batch(s, N, stream, "reference cmd + swing", [&](auto scalar, const LaunchCtx& L) {
+    using T = decltype(scalar);
+    CmdRefArgs<T> a;
+    cmd_ref_args(a, s, N, q, v, cmd, normals, height, reset, trunk, w_des, vdot_des, com, ref);
+    SwingArgs<T> sa;
+    swing_args(sa, s, mask, swing, foot);
+    return k_reference_cmd_swing<T>(L, dev_model<T>(s), (const DevRefParams<T>*)s->d_ref, a, sa);
+  });
+}

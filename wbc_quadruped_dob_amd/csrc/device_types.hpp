@@ -348,6 +348,23 @@ template <class T> struct OdomArgs {   // base_estimate_kernel
 };
 // gait_estimated_odom_kernel: o.contact == e.c.contact, o.mask == e.g.mask, o.normals == e.c.normals; rows 0-2 of e.g.q, e.g.v are never read
 template <class T> struct GaitEstimatedOdomArgs { GaitEstimatedArgs<T> e; OdomIO<T> o; };
+// trunk reference from the velocity command (cmd_ref.hip.hpp): the parameters BY VALUE like the swing gains (wbc_solver_set_trunk_params only fills
+// the solver's host copy); dt (the solver's), pi, two_pi and cos_yl = cos(yaw_leash) are formed on the host in double and rounded to T
+constexpr int TRUNK_WORDS = 6;      // trunk [TRUNK_WORDS][N]: x, y, psi, z_s, s_x, s_y
+constexpr int TRUNKREF_WORDS = 10;  // ref [TRUNKREF_WORDS][N]: c_ref (3), cd_ref (3), quat_des (x, y, z, w)
+template <class T> struct DevTrunkParams { T height, leash, a_s, tilt, nz_min, det_min, dt, pi, two_pi, cos_yl; };
+template <class T> struct CmdRefArgs {   // cmd_reference_kernel; cmd_swing_reference_kernel takes this + SwingArgs
+  size_t N;
+  const T* q; const T* v; const T* cmd;    // cmd [GAIT_CMD_WORDS][N]: rows 0-2 are read
+  const T* normals; const T* height;       // [12][N], [4][N]: the plane under every foot
+  const int* reset;                        // [N] or null
+  T* trunk;                                // [TRUNK_WORDS][N] in/out
+  T* w_des; T* vdot_des;
+  T* com;   // [6][N] or null
+  T* ref;   // [TRUNKREF_WORDS][N] or null
+  unsigned long long jpack;   // see SweepArgs::jpack
+  DevTrunkParams<T> P;
+};
 
 // MODE bits of dyn_sweep_kernel (dyn_sweep.hip.hpp)
 constexpr int SW_MATS = 1;  // write M, h, Jc

@@ -137,5 +137,10 @@ template <class T> hipError_t k_gait_estimated_terrain_select(const LaunchCtx& L
 // is that law, then k_gait_estimated with the estimated base rows handed over in registers -- one launch
 template <class T> hipError_t k_base_estimate(const LaunchCtx& L, const DevModel<T>* model, const OdomArgs<T>& a);
 template <class T> hipError_t k_gait_estimated_odom(const LaunchCtx& L, const DevModel<T>* model, const GaitEstimatedOdomArgs<T>& a);
+// trunk reference from the velocity command (cmd_ref.hip.hpp): cmd_reference_kernel<T> is k_reference with the plan formed on the device from cmd and
+// the foot planes (trunk advances in place); cmd_swing_reference_kernel<T> is the same with the swing law applied before the joint rows are stored
+template <class T> hipError_t k_reference_cmd(const LaunchCtx& L, const DevModel<T>* model, const DevRefParams<T>* G, const CmdRefArgs<T>& a);
+template <class T> hipError_t k_reference_cmd_swing(const LaunchCtx& L, const DevModel<T>* model, const DevRefParams<T>* G, const CmdRefArgs<T>& a,
+                                                    const SwingArgs<T>& sa);
 
 }  // namespace wbc

@@ -53,6 +53,7 @@ struct wbc_solver {
   wbc_contact_params contact_est;   // the thresholds of the contact estimate (wbc_solver_set_contact_params; a kernel argument by value), the defaults at creation
   wbc_foothold_params foothold;     // the weights of the foothold selection (wbc_solver_set_foothold_params; a kernel argument by value), the defaults at creation
   wbc_odom_params odom;             // the gains of the base estimate (wbc_solver_set_odom_params; kernel arguments by value), the defaults at creation
+  wbc_trunk_params trunk;           // the trunk reference from the command (wbc_solver_set_trunk_params; kernel arguments by value), the defaults at creation
   void* d_stage_one = nullptr;      // the fp64 single-robot helpers' staging: STAGE_ONE_DOUBLES doubles + STAGE_ONE_INTS ints
   // torque-limit post-pass (wbc_limit_torques_batch): the limits travel as a kernel argument like the score weights
   double tau_max[WBC_MAXV];  // caller's joint order, HUGE_VAL = none; the model's effort limits at creation
